@@ -16,14 +16,32 @@ reference init this 30-block net starts at loss 13 with |logits| ~ 50 and
 the Keras clip zeroes the gradient of most images; the line reports the
 loss and the fraction of images with a live gradient, and fails below 0.9).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs the warm-up steps, times the K steps and prints the
+result line (metric, value, ms_per_step, the losses and the live-gradient
+fraction of the timed steps); its `roofline` and `cpu_baseline` are null.
+The multi-stage configs (he32, he32_bf16) are the exception: their `roofline`
+is the whole step's conv FLOP/s, arithmetic on the timed steps' own time, and
+stays in the plain line.
+--full adds what takes runs of its own after the timed region: the
+instrumented steps and the random-operand leg behind `roofline`, and the CPU
+baselines (--timed-steps, --block-reps, --no-random-leg, --no-cpu-baseline and
+--cpu-threads shape those legs and mean nothing without --full).
+
+--dump-outputs DIR writes what the last timed step computed, as float32
+DIR/<name>.npy: loss, grads (the flat gradient), probs (the batch's softmax
+outputs; not for the multi-stage configs) and params (the flat parameters
+after that step's Adam update); probs alone for the forward-only configs.
+Inputs and initial weights are seeded, so two builds given the same arguments
+can be compared output for output.
 
 --config c2_eval times the forward pass alone (the metric's model in
 evaluation: asr_net_forward on the forward-only workspace, probabilities of
 512 images per step; reference: Training._evaluate, training/training.py:670-706).
 
-The line's `roofline` is measured on the timed step's own kernels: after the
-timed region, --timed-steps more steps run with ASR_VARIANT_TIMED, which
+With --full the line's `roofline` is measured on the timed step's own kernels:
+after the timed region, --timed-steps more steps run with ASR_VARIANT_TIMED, which
 records HIP events on the launch stream around the block launches inside
 asr_net_forward_backward (the single k_fwd3_stack / k_bwd3_stack launches at
 C2); their averages give `avg_us` and `frac`.  The random-operand timing of
@@ -57,6 +75,7 @@ BF16_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA (spec)
 F32_PEAK_TFLOPS = 157.3
 THETA_SCALE, FC_SCALE = 0.5, 0.1  # bench init (see the module docstring)
 N_BATCHES = 8
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much
 
 CONFIGS = {
     # name: (C, L, per-GPU batch, dtype, description, integrator, mode)
@@ -111,6 +130,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS) + sorted(STAGE_CONFIGS))
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure the roofline (instrumented steps, random-operand leg) "
+                         "and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--block-reps", type=int, default=50)
     ap.add_argument("--timed-steps", type=int, default=10,
                     help="instrumented steps after the timed region: in-step kernel times for the roofline")
@@ -152,6 +176,20 @@ def bench_params(C, L):
         off += n + C
     flat[off:off + C * 10] *= FC_SCALE
     return flat
+
+
+def dump_outputs(directory, tensors):
+    """--dump-outputs: every tensor of `tensors` (name -> device tensor) as
+    float32 `directory`/<name>.npy, DUMP_LIMIT_BYTES in all: an array above
+    its share of the limit is cut to a fixed (seed 0) sorted sample of its
+    flattened elements, the same sample in every run."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (4 * len(tensors))  # elements per array
+    for name, t in tensors.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def block_roofline(rt, lib, C, N, dtype_name, reps, h, integrator="euler"):
@@ -611,6 +649,8 @@ def stages_main(args):
     torch.cuda.synchronize()
     elapsed = distributed.max_over_ranks(time.perf_counter() - t0)
     value = N * world * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": out, "grads": ex.grads, "params": params})
     if rank == 0:
         # conv FLOPs per image, forward: stem, transitions (3x3 + 1x1), identity blocks; train = 3x forward
         fl, Hc, Cp = 2 * 9 * 3 * stages[0][0] * 32 * 32, 32, stages[0][0]
@@ -639,7 +679,7 @@ def stages_main(args):
                                    "stem, head, reductions, Adam)"},
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out_line["cpu_baseline"] = cpu_stages_baseline(args.cpu_threads or host_threads(), stages,
                                                            params.cpu().numpy(), h)
         print(json.dumps(out_line), flush=True)
@@ -732,20 +772,24 @@ def main():
     live = -distributed.max_over_ranks(-live_fraction()) if train else None  # min over ranks
     if train:
         ex.check_status()  # blocking: every launch completed
+    if rank == 0 and args.dump_outputs:  # what the last timed step handed back, before anything else runs
+        dump_outputs(args.dump_outputs, {"loss": ex.loss, "grads": ex.grads, "probs": ex.probs, "params": params}
+                     if train else {"probs": out})
 
-    # the timed step's own block kernels: events inside instrumented steps (all ranks take part)
-    ex.variant = rt.ASR_VARIANT_TIMED | base_variant
+    # --full: the timed step's own block kernels: events inside instrumented steps (all ranks take part)
     kts = []
-    for _ in range(max(1, args.timed_steps)):
-        step()
-        kts.append(ex.kernel_times())
-    ex.variant = base_variant
+    if args.full:
+        ex.variant = rt.ASR_VARIANT_TIMED | base_variant
+        for _ in range(max(1, args.timed_steps)):
+            step()
+            kts.append(ex.kernel_times())
+        ex.variant = base_variant
     degraded = None
     if train:
         ex.check_status()
-        degraded = rt.stack_status(reset=True)  # hand-offs of the timed + instrumented steps that degraded
+        degraded = rt.stack_status(reset=True)  # hand-offs of the timed (+ instrumented) steps that degraded
 
-    if rank == 0:
+    def roofline():  # --full, rank 0
         def avg(key):
             vals = [k[key] for k in kts if k[key] is not None]
             return sum(vals) / len(vals) * 1e-6 if vals else None
@@ -820,8 +864,12 @@ def main():
         co = co_bound(args.config, flops, bytes_blk, t_blk, train, dtype_name)
         if co:
             roof.update(co)
+        return roof
+
+    if rank == 0:
+        roof = roofline() if args.full else None
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and integrator == "euler":
+        if args.full and world == 1 and not args.no_cpu_baseline and integrator == "euler":
             threads = args.cpu_threads or host_threads()
             if args.config == "c2":
                 cpu = cpu_baseline(threads)

@@ -138,7 +138,7 @@ def test_bench_two_ranks_one_device(tmp_path):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.update({"NCCL_SOCKET_IFNAME": "lo", "NCCL_IB_DISABLE": "1"})
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline", "--share-device", "--block-reps", "2"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--share-device", "--block-reps", "2"]
     p = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
                          start_new_session=True)
     try:
