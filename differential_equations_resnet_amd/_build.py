@@ -5,6 +5,7 @@ repository snapshot to the GPU box; nothing is installed anywhere.
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -16,8 +17,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libasr.so")
 SOURCES = ["asr_theta.hip", "asr_block_mfma.hip", "asr_conv_f32.hip", "asr_stem_head.hip", "asr_api.hip", "asr_dist.hip", "asr_deep16.hip", "asr_stages.hip"]
-HEADERS = ["asr_common.h", "asr_device.h", os.path.join("..", "..", "include", "asr.h")]
 ARCH = "gfx950"
+
+
+def headers() -> list[str]:
+    """Every header a source may include: an edit to any of them rebuilds the library."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "asr.h")]
 
 
 def hipcc() -> str:
@@ -31,7 +36,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, h) for h in HEADERS]
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + headers()
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

@@ -11,111 +11,10 @@
 #include <vector>
 
 #include "asr_common.h"
+#include "asr_internal.h"
 
 namespace asr {
-// asr_theta.hip
-long theta_count(int C, int kind, int antisymmetric);
-int param_map(int C, int kind, int antisymmetric, int32_t* w_src, int32_t* theta_dst);
-int param_is_antisymmetric(int kind, int antisymmetric);
-int param_map_transpose(int C, const int32_t* w_src, int32_t* w_bwd);
-int reduce_and_project(const float* slabs, int P, long E, int Cb, const int32_t* theta_dst, long n_theta,
-                       float* dtheta, float* dbias, float* dw_out, float* ws, hipStream_t s);
-size_t reduce_ws_bytes(int P, long ES);
-int reduce_groups(int P);
-int reduce_slabs_to_groups(const float* slabs, int P, long ES, float* grp, hipStream_t s);
-int reduce_slab_layers(const float* slabs, long slab_stride, int P, long ES, float* grp, long grp_stride, int L,
-                       hipStream_t s);
-int project_layers(float* grp, long grp_stride, int G, long E, int Cb, const int32_t* theta_dst, long n_theta,
-                   int L, float* out, long out_stride, hipStream_t s);
-// asr_block_mfma.hip
-int block_fwd_mfma(int mode, const void* x, const void* resid, void* y, uint8_t* mask, const void* w,
-                   const float* bias, float h, int N, int H, int W, int C, hipStream_t s);
-// relu_dx (optional): dx *= [x > 0] when the kernel supports it (*relu_done = 1).
-// fold_* (optional): pass 1 of another slab set's reduction (fold_P slabs ->
-// reduce_groups(fold_P) group rows at fold_grp), folded into the kernel when
-// it supports it (*fold_done = 1); else the caller reduces them itself.
-int block_bwd_mfma(int mode, const void* dy, const void* x, const uint8_t* mask, const void* w, float h,
-                   float two_gamma, int N, int H, int W, int C, void* dx, float* slabs, int* nslabs, const void* extra,
-                   int skip_dy, hipStream_t s, int relu_dx = 0, int* relu_done = nullptr,
-                   const float* fold_slabs = nullptr, int fold_P = 0, float* fold_grp = nullptr,
-                   int* fold_done = nullptr, int accum = 0);
-int stem_wgrad_mfma(const void* img, int input_u8, const void* dz1, int N, int H, int W, int Cin, int C, float mean,
-                    float inv_std, int use_norm, float* slabs, int* nslabs, hipStream_t s);
-bool stem_wgrad_mfma_supported(int Cin, int H, int W, int C);
-int stem_fwd_mfma(const void* img, int input_u8, const float* w1, const float* b1, int N, int H, int W, int Cin, int C,
-                  float mean, float inv_std, int use_norm, void* out, hipStream_t s);
-bool stem_fwd_mfma_supported(int Cin, int H, int W, int C);
 static bool mfma_supported(int C, int W) { return (C == 16 || C == 32 || C == 64) && W == 32; }
-// asr_conv_f32.hip: bf16 Euler blocks at any stage width (W in {32, 16, 8}), the multi-stage nets' path
-bool convb_supported(int W, int C);
-int convb_forward(const void* x, void* y, uint8_t* mask, const void* w, const float* bias, float h, int N, int H, int W,
-                  int C, hipStream_t s, bool conv_only = false);
-int convb_backward(const void* dy, const uint8_t* mask, const void* x, const void* w, float h, float two_gamma, int N,
-                   int H, int W, int C, void* dx, bool need_w, float* slabs, int* nslabs, hipStream_t s,
-                   bool conv_only = false);
-// asr_deep16.hip
-bool deep16_supported(int H, int W, int C);
-bool block_stack_fwd_supported(int N, int H, int W, int C);
-bool block_stack_bwd_supported(int N, int H, int W, int C);
-int block_stack_fwd_rk2_mfma(const void* x0, void* ys, void* xm, long y_stride, uint8_t* masks, uint8_t* masks2,
-                             long mask_stride, const void* w, long w_stride, const float* bias, long bias_stride,
-                             float h, int N, int H, int W, int C, int L, hipStream_t s);
-int block_stack_bwd_grid(int N);
-int theta_dst_tile_major(const int32_t* in, long n, int C, int32_t* out, hipStream_t s);
-int stack_done_words(int L);
-int stack_bwd_reduce_rest(const float* slabs, long slab_stride, int grid, long ES, float* grp, long grp_stride, int L,
-                          int lfold, const unsigned* done, hipStream_t s);
-int block_stack_bwd_mfma(void* dbuf0, void* dbuf1, const void* xs, long x_stride, const uint8_t* masks,
-                         long mask_stride, const void* w, long w_stride, float h, float two_gamma, int N, int H, int W,
-                         int C, int L, int ro0, float* slabs, long slab_stride, float* grp, long grp_stride,
-                         unsigned* done, int* lfold_out, hipStream_t s, const void* xm = nullptr,
-                         const uint8_t* masks2 = nullptr, void* gbuf = nullptr, const void* gtop = nullptr,
-                         int fold = 1, int pair = 0);
-long stack_slab_floats(int C, int pair);
-int theta_dst_pair(const int32_t* in, long n_theta, int C, int32_t* out, hipStream_t s);
-int theta_dst_pair_host(const int32_t* in, long n_theta, int C, int32_t* out);
-int block_stack_fwd_mfma(const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride, const void* w,
-                         long w_stride, const float* bias, long bias_stride, float h, int N, int H, int W, int C, int L,
-                         hipStream_t s, int slots = 0);
-int deep16_forward(const void* x0, void* y0, long y_stride, uint8_t* mask0, long mask_stride, const void* wpack,
-                   const float* bias, long bias_stride, float h, int N, int L, bool store_all, hipStream_t s);
-int theta_to_w_bf16(const float* theta, long theta_stride, int L, int C, const int32_t* w_src, float gamma, void* w,
-                    long w_stride, bool balance, hipStream_t s, const int32_t* theta_dst = nullptr,
-                    long n_theta = 0);
-size_t deep16_slab_bytes(int N, int L);
-int deep16_backward(void* dbufA, void* dbufB, const void* xs, long x_stride, const uint8_t* masks, long mask_stride,
-                    const void* wpack, float h, float two_gamma, int N, int L, float* slabs, int* slab_rows,
-                    int* dx0_in_b, hipStream_t s);
-// asr_conv_f32.hip
-int conv_f32(int fmode, const void* xin, void* out, uint8_t* mask, const float* w, const float* bias, float h,
-             float two_gamma, const float* dy, int N, int H, int W, int Ci, int Co, int out_bf16, hipStream_t s,
-             const float* extra = nullptr);
-int make_dz(int fmode, const void* dy, const uint8_t* mask, const void* relu_src, float h, int N, int H, int W, int C,
-            int src_bf16, float* dz, hipStream_t s);
-int wgrad_f32(const void* x, int x_bf16, const float* dz, int N, int H, int W, int Ci, int Co, float* slabs,
-              int* nslabs, hipStream_t s, int K = 3);
-int conv_f32_k(int fmode, int K, const void* xin, void* out, uint8_t* mask, const float* w, const float* bias, float h,
-               float two_gamma, const float* dy, int N, int H, int W, int C, hipStream_t s, const float* extra);
-int wgrad_f32_chunks(int N, int H);
-int f32_block_slab_rows(int N, int H, int W, int C);
-bool conv32_fused_bwd_supported(int W, int C);
-int conv32_bwd_fused(const float* dy, const uint8_t* mask, float h, const float* x, const float* w, float two_gamma,
-                     const float* extra, bool skip_dy, int N, int H, int W, int C, float* dx, bool need_w,
-                     float* slabs, int* nslabs, hipStream_t s);
-// asr_stem_head.hip
-bool stem_supported(int Cin, int H, int W, int C);
-int stem_forward(const void* img, int input_u8, const float* w1, const float* b1, int N, int H, int W, int Cin, int C,
-                 float mean, float inv_std, int use_norm, void* out, int out_bf16, hipStream_t s);
-int stem_wgrad(const void* img, int input_u8, const void* dx1, const void* x1, int act_bf16, int N, int H, int W,
-               int Cin, int C, float mean, float inv_std, int use_norm, float* slabs, int* nslabs, hipStream_t s);
-int head(const void* xL, int act_bf16, const float* fck, const float* fcb, const float* targets, int N, int HW, int C,
-         int K, float* probs, float* loss_per, float* dlogits, float* gap, void* dxL, hipStream_t s,
-         void* growL = nullptr);
-int head_param_grads(const float* gap, const float* dlogits, int N, int C, int K, float* dfck, float* dfcb,
-                     const float* loss_per, float* loss_out, hipStream_t s);
-
-constexpr int kMaxSlabsApi = 512;  // matches asr_block_mfma.hip kMaxBlockSlabs
-enum { F_EULER = 0, F_CONV = 1, F_RELU = 2, B_EULER = 3, B_CONV = 4 };
 
 static int check_shape(int N, int H, int W, int C) {
   if (N < 1 || H < 1 || W < 1 || C < 1) return fail(ASR_E_ARG, "bad shape N=%d H=%d W=%d C=%d", N, H, W, C);
@@ -137,7 +36,7 @@ static BwdWs bwd_ws_layout(int N, int H, int W, int C, int dtype, int stages = 1
   BwdWs b{};
   const long E = (long)K * K * C * C;
   const long P = (long)N * H * W * C;
-  const int nsl = slab_rows >= 0 ? slab_rows : kMaxSlabsApi * stages;
+  const int nsl = slab_rows >= 0 ? slab_rows : kMaxBlockSlabs * stages;
   size_t off = 0;
   b.dz = off;
   if (dtype == ASR_F32) off += align_up((size_t)P * 4, 256);
@@ -463,13 +362,13 @@ static NetLayout net_layout(const asr_net_config* c) {
   L.f32_rows = f32 ? f32_block_slab_rows(c->N, c->H, c->W, C) : 0;
   const BwdWs bw = bwd_ws_layout(c->N, c->H, c->W, C, c->dtype, L.stages, 3, f32 ? 0 : -1);
   const long E1 = 9L * c->Cin * C;
-  const size_t stem_ws = align_up((size_t)L.P * 4, 256) + align_up((size_t)kMaxSlabsApi * (E1 + C) * 4, 256) +
-                         align_up(reduce_ws_bytes(kMaxSlabsApi, E1 + C), 256);
+  const size_t stem_ws = align_up((size_t)L.P * 4, 256) + align_up((size_t)kMaxBlockSlabs * (E1 + C) * 4, 256) +
+                         align_up(reduce_ws_bytes(kMaxBlockSlabs, E1 + C), 256);
   L.bwdws = take(tr ? std::max(bw.total, stem_ws) : 0);
   // odd Euler blocks' slabs (even ones use the backward workspace's): a
   // block's slabs stay readable while the next block's kernel reduces them
-  L.slabs2 = take(tr && !f32 ? (size_t)L.stages * kMaxSlabsApi * (L.E + C) * 4 : 0);  // every other block's slabs
-  const int rows = f32 ? L.stages * L.f32_rows : L.stages * kMaxSlabsApi;
+  L.slabs2 = take(tr && !f32 ? (size_t)L.stages * kMaxBlockSlabs * (L.E + C) * 4 : 0);  // every other block's slabs
+  const int rows = f32 ? L.stages * L.f32_rows : L.stages * kMaxBlockSlabs;
   L.grp_stride = (long)reduce_groups(rows) * (L.E + C);
   L.grp = take(tr ? (size_t)c->L * L.grp_stride * 4 : 0);
   L.slab_stride = (long)rows * (L.E + C);
@@ -723,7 +622,7 @@ static StackWs stack_ws_layout(int N, int H, int W, int C, int L, int dtype, boo
     w.slabs = off;
     off += align_up(deep16_slab_bytes(N, L), 256);
     w.grp = off;
-    off += align_up((size_t)L * reduce_groups(kMaxSlabsApi) * ES * 4, 256);
+    off += align_up((size_t)L * reduce_groups(kMaxBlockSlabs) * ES * 4, 256);
   } else if (w.stack64) {  // slabs [L][grid][ES] (tile-major dW), group rows, counters, tile-major theta map
     w.slabs = off;
     off += align_up((size_t)L * w.grid * ES * 4, 256);
@@ -1214,7 +1113,7 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
   unsigned char* sw = b + L.bwdws;
   float* dz = (float*)sw;
   float* slabs = (float*)(sw + align_up((size_t)L.P * 4, 256));
-  float* red = (float*)(sw + align_up((size_t)L.P * 4, 256) + align_up((size_t)kMaxSlabsApi * (E1 + C) * 4, 256));
+  float* red = (float*)(sw + align_up((size_t)L.P * 4, 256) + align_up((size_t)kMaxBlockSlabs * (E1 + C) * 4, 256));
   int nsl = 0;
   const float inv_std = cfg->use_norm ? 1.f / cfg->divide_by_stddev : 1.f;
   if (L.fast_stem && bf && !dz1_fused && !stem_v1 && stem_wgrad_mfma_supported(cfg->Cin, H, W, C) && L.P % 8 == 0) {

@@ -16,7 +16,8 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 namespace asr {
 
-// thread-local error message (asr_last_error)
+// thread-local error message (asr_last_error).  Defined in asr_theta.hip; declared here, not in
+// asr_internal.h with the other cross-file host functions, because hip_check below calls fail.
 void set_error(const char* fmt, ...);
 int fail(int code, const char* fmt, ...);
 
@@ -33,20 +34,12 @@ inline int hip_check(hipError_t e, const char* what) {
 
 #define ASR_LAUNCH_CHECK(name) ASR_TRY(::asr::hip_check(hipGetLastError(), name))
 
-int cu_count();
-
-// A network / stage workspace must live on the current device: its layout (the
-// weight-gradient slab rows, hence every offset after them) follows the CU
-// count of the device current when it was sized, and the kernels size their
-// grids by the device current at launch.  ASR_E_WORKSPACE, before any launch,
-// when ws is not device memory of the current device.
-int check_ws_device(const void* ws, const char* who);
-
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // One launch of the balanced bf16 weight pack for several layer sets (the
 // multi-stage net's stages, asr_stages.hip): one workgroup per layer, so the
-// stages' packs run side by side (asr_theta.hip, k_theta_to_w_pack_bal).
+// stages' packs run side by side (theta_to_w_bf16_jobs, asr_internal.h;
+// k_theta_to_w_pack_bal, asr_theta.hip).
 struct PackJob {
   const float* theta;
   long theta_stride;
@@ -60,8 +53,6 @@ struct PackJob {
   const int32_t* theta_dst;
   long n_theta;
 };
-constexpr int kMaxPackJobs = 16;
-int theta_to_w_bf16_jobs(const PackJob* jobs, int njobs, hipStream_t s);
 
 // Slab layout of the pair-local C=64 stacked backward (k_bwd3_stack<..., PAIR>,
 // asr_block_mfma.hip): for an antisymmetric operator every theta pulls back

@@ -10,10 +10,9 @@
 // a regular 3x3 conv with C_in = 3).  It shares the mask layout, the theta
 // projection and the API with the bf16 path.
 #include "asr_common.h"
+#include "asr_internal.h"
 
 namespace asr {
-
-enum { F_EULER = 0, F_CONV = 1, F_RELU = 2, B_EULER = 3, B_CONV = 4 };
 
 // One wave = (n, y, 16-pixel tile, 16-channel tile).  Lane (g = lane>>4,
 // lx = lane&15) computes pixel 16*pt+lx, channels 16*ot+4g .. +3 (the MFMA D
@@ -488,8 +487,7 @@ static int conv32_dispatch(int C, int W, const void* xin, void* out, uint8_t* ma
 template <int C, int W>
 static int wgrad32_grid(int N, int H) {
   const long items = (long)N * ((H + 3) / 4);
-  int cus = cu_count();
-  if (cus <= 0) cus = 256;
+  const int cus = launch_cus();
   const int per_cu = std::max(1, std::min(2, (int)((160 * 1024) / wgrad32_lds<C, W>())));
   // at least minb bands per workgroup at C = 32 / 64: a slab row is 37 / 148 KB, written and read back
   constexpr int minb = C == 64 ? 16 : C == 32 ? 8 : 1;  // (profiles/r05al_f32_wgrad_rows_ab.txt)
@@ -621,7 +619,7 @@ int conv32_bwd_fused(const float* dy, const uint8_t* mask, float h, const float*
   return fail(ASR_E_UNSUPPORTED, "conv f32 fused backward: C=%d W=%d", C, W);
 }
 
-// number of row chunks used by the fp32 wgrad (bounded by kMaxSlabs in the
+// number of row chunks used by the fp32 wgrad (bounded by kMaxBlockSlabs in the
 // workspace sizing of the callers)
 int wgrad_f32_chunks(int N, int H) {
   const long R = (long)N * H;
@@ -849,8 +847,7 @@ template <int C, int W, int MODE>
 static int launch_convb(const bf16* xin, bf16* out, uint8_t* mask, const bf16* w, const float* bias, float h,
                         float two_gamma, const bf16* dy, int N, int H, const uint8_t* dmask, hipStream_t s) {
   const long items = (long)N * ((H + 3) / 4);
-  int cus = cu_count();
-  if (cus <= 0) cus = 256;
+  const int cus = launch_cus();
   const long grid = std::max<long>(1, std::min<long>(items, 4L * cus));  // 4 persistent workgroups per CU (r05r)
   hipLaunchKernelGGL((k_convb<C, W, MODE>), dim3((unsigned)grid), dim3(256), 0, s, xin, out, mask, w, bias, h,
                      two_gamma, dy, N, H, dmask);

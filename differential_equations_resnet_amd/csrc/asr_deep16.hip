@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "asr_common.h"
+#include "asr_internal.h"
 #include "asr_device.h"
 
 namespace asr {
@@ -651,8 +652,7 @@ bool deep16_supported(int H, int W, int C) { return C == deep::C && H == deep::H
 int deep16_forward(const void* x0, void* y0, long y_stride, uint8_t* mask0, long mask_stride, const void* wpack,
                    const float* bias, long bias_stride, float h, int N, int L, bool store_all, hipStream_t s) {
   if (L < 1 || N < 1) return fail(ASR_E_ARG, "deep16_forward: bad N=%d L=%d", N, L);
-  int cus = cu_count();
-  if (cus <= 0) cus = 256;
+  const int cus = launch_cus();
   const int grid = std::max(1, std::min(N, 2 * cus));
   const size_t lds = 2 * (size_t)deep::TILE + deep::ROWB;
 #define ASR_FWD16(SA, MK)                                                                                        \
@@ -677,8 +677,7 @@ extern "C" int asr_debug_deep16_trace(void* dst, size_t bytes) {
 #endif
 
 int deep16_slab_rows(int N) {
-  int cus = cu_count();
-  if (cus <= 0) cus = 256;
+  const int cus = launch_cus();
   const int P = std::max(1, std::min(N, cus));
   return (P + 31) / 32 * 32;
 }
@@ -692,8 +691,7 @@ int deep16_backward(void* dbufA, void* dbufB, const void* xs, long x_stride, con
                     const void* wpack, float h, float two_gamma, int N, int L, float* slabs, int* slab_rows,
                     int* dx0_in_b, hipStream_t s) {
   if (L < 1 || N < 1) return fail(ASR_E_ARG, "deep16_backward: bad N=%d L=%d", N, L);
-  int cus = cu_count();
-  if (cus <= 0) cus = 256;
+  const int cus = launch_cus();
   const int P = std::max(1, std::min(N, cus));
   const int PS = deep16_slab_rows(N);
   auto kern = two_gamma != 0.f ? deep::k_bwd16_fused<true> : deep::k_bwd16_fused<false>;

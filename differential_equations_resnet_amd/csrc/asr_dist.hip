@@ -19,6 +19,7 @@
 #include <mutex>
 
 #include "asr_common.h"
+#include "asr_internal.h"
 
 namespace asr {
 namespace {

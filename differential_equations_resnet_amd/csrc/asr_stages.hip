@@ -30,84 +30,13 @@
 #include <vector>
 
 #include "asr_common.h"
+#include "asr_internal.h"
 
 namespace asr {
-// asr_theta.hip
-long theta_count(int C, int kind, int antisymmetric);
-int param_map(int C, int kind, int antisymmetric, int32_t* w_src, int32_t* theta_dst);
-int param_is_antisymmetric(int kind, int antisymmetric);
-int param_map_transpose(int C, const int32_t* w_src, int32_t* w_bwd);
-int reduce_and_project(const float* slabs, int P, long E, int Cb, const int32_t* theta_dst, long n_theta,
-                       float* dtheta, float* dbias, float* dw_out, float* ws, hipStream_t s);
-size_t reduce_ws_bytes(int P, long ES);
-int reduce_groups(int P);
-int f32_block_slab_rows(int N, int H, int W, int C);
-int project_layers(float* grp, long grp_stride, int G, long E, int Cb, const int32_t* theta_dst, long n_theta,
-                   int L, float* out, long out_stride, hipStream_t s);
-int reduce_slab_layers(const float* slabs, long slab_stride, int P, long ES, float* grp, long grp_stride, int L,
-                       hipStream_t s);
-// asr_conv_f32.hip: the bf16 blocks at any stage width, bf16 <-> fp32
-bool convb_supported(int W, int C);
-int convb_forward(const void* x, void* y, uint8_t* mask, const void* w, const float* bias, float h, int N, int H, int W,
-                  int C, hipStream_t s, bool conv_only = false);
-int convb_backward(const void* dy, const uint8_t* mask, const void* x, const void* w, float h, float two_gamma, int N,
-                   int H, int W, int C, void* dx, bool need_w, float* slabs, int* nslabs, hipStream_t s,
-                   bool conv_only = false);
-int convert_bf16_f32(const void* src, void* dst, long n, int to_f32, hipStream_t s);
-bool stage_img_supported(int H, int W, int C);
-int stage_img_forward(const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride, const void* w,
-                      long w_stride, const float* bias, long bias_stride, float h, int N, int H, int W, int C, int L,
-                      hipStream_t s);
-int stage_img_backward(const void* dyL, void* dys, long d_stride, void* dx0, const uint8_t* masks, long mask_stride,
-                       const void* w, long w_stride, float h, float two_gamma, int N, int H, int W, int C, int L,
-                       hipStream_t s);
-bool stage_img32_supported(int H, int W, int C);
-int stage_img32_forward(const float* x0, float* ys, long y_stride, uint8_t* masks, long mask_stride, const float* w,
-                        long w_stride, const float* bias, long bias_stride, float h, int N, int H, int W, int C, int L,
-                        hipStream_t s);
-int stage_img32_backward(const float* dyL, float* dys, long d_stride, float* dx0, const uint8_t* masks,
-                         long mask_stride, const float* w, long w_stride, float h, float two_gamma, int N, int H, int W,
-                         int C, int L, hipStream_t s);
-int wgrad32_layers(const float* x0, long x_stride, const float* dys, long d_stride, const uint8_t* masks,
-                   long mask_stride, float h, int N, int H, int W, int C, int L, float* slabs, long slab_stride,
-                   int* nslabs, hipStream_t s);
-int wgradb_layers(const void* x0, long x_stride, const void* dys, long d_stride, const uint8_t* masks,
-                  long mask_stride, float h, int N, int H, int W, int C, int L, float* slabs, long slab_stride,
-                  int* nslabs, hipStream_t s);
-// asr_deep16.hip: the C = 16, 32 x 32 bf16 stage as one fused forward / backward launch
-bool deep16_supported(int H, int W, int C);
-int deep16_forward(const void* x0, void* y0, long y_stride, uint8_t* mask0, long mask_stride, const void* wpack,
-                   const float* bias, long bias_stride, float h, int N, int L, bool store_all, hipStream_t s);
-size_t deep16_slab_bytes(int N, int L);
-int deep16_backward(void* dbufA, void* dbufB, const void* xs, long x_stride, const uint8_t* masks, long mask_stride,
-                    const void* wpack, float h, float two_gamma, int N, int L, float* slabs, int* slab_rows,
-                    int* dx0_in_b, hipStream_t s);
-// asr_theta.hip
-int reduce_slabs_to_groups(const float* slabs, int P, long ES, float* grp, hipStream_t s);
-// asr_api.hip
-int conv_backward_keep_slabs(const void* dy, const void* x, const uint8_t* mask, const void* w, float h, float gamma,
-                             int N, int H, int W, int C, void* dx, void* ws, float* slabs, int* nsl, hipStream_t s);
-// asr_stem_head.hip
-bool stem_supported(int Cin, int H, int W, int C);
-int stem_forward(const void* img, int input_u8, const float* w1, const float* b1, int N, int H, int W, int Cin, int C,
-                 float mean, float inv_std, int use_norm, void* out, int out_bf16, hipStream_t s);
-int stem_wgrad_mfma(const void* img, int input_u8, const void* dz1, int N, int H, int W, int Cin, int C, float mean,
-                    float inv_std, int use_norm, float* slabs, int* nslabs, hipStream_t s);
-bool stem_wgrad_mfma_supported(int Cin, int H, int W, int C);
-int relu_grad_bf16(void* d, const void* x, long n, hipStream_t s);
-int stem_wgrad(const void* img, int input_u8, const void* dx1, const void* x1, int act_bf16, int N, int H, int W,
-               int Cin, int C, float mean, float inv_std, int use_norm, float* slabs, int* nslabs, hipStream_t s);
-int head(const void* xL, int act_bf16, const float* fck, const float* fcb, const float* targets, int N, int HW, int C,
-         int K, float* probs, float* loss_per, float* dlogits, float* gap, void* dxL, hipStream_t s,
-         void* growL = nullptr);
-int head_param_grads(const float* gap, const float* dlogits, int N, int C, int K, float* dfck, float* dfcb,
-                     const float* loss_per, float* loss_out, hipStream_t s);
-
 namespace {
 
 constexpr int kTK = 3;              // the transition's kxk (the builder's kernel_size; 3 in every reference config)
 constexpr int kMaxTransChunks = 256;  // wgrad row chunks
-constexpr int kMaxStemSlabs = 512;    // asr_stem_head.hip stem_grid bound
 
 struct TGeom {
   int Ho, Wo, pt, pl;
@@ -738,8 +667,7 @@ int launch_trans_fwd_lds(const T* x, T* y, uint8_t* mask, const float* k2, const
                          const float* b1, int N, int H, hipStream_t s) {
   using G = TFw<CI, CO, WO>;
   const long items = (long)N * (H / 2 / G::BRO);
-  int cus = cu_count();
-  if (cus <= 0) cus = 256;
+  const int cus = launch_cus();
   const int grid = (int)std::max<long>(1, std::min<long>(items, 2L * cus));  // 2 workgroups per CU
   hipLaunchKernelGGL((k_trans_fwd_lds<CI, CO, WO, T>), dim3(grid), dim3(64 * G::NW), G::LDS, s, x, y, mask, k2, b2, k1,
                      b1, N, H);
@@ -877,8 +805,7 @@ int launch_trans_dgrad_lds(const T* dy, const uint8_t* mask, const float* k2, co
                            int H, hipStream_t s) {
   using G = TDg<CI, CO, WO>;
   const long items = (long)N * (H / G::BR);
-  int cus = cu_count();
-  if (cus <= 0) cus = 256;
+  const int cus = launch_cus();
   const int grid = (int)std::max<long>(1, std::min<long>(items, (long)cus));  // 1 workgroup per CU
   hipLaunchKernelGGL((k_trans_dgrad_lds<CI, CO, WO, T>), dim3(grid), dim3(512), G::LDS, s, dy, mask, k2, k1, dx, N, H);
   ASR_LAUNCH_CHECK("k_trans_dgrad_lds");
@@ -908,8 +835,7 @@ int launch_trans_wgrad_lds(const T* dy, const uint8_t* mask, const T* x, float* 
                            int max_rows, int* rows_out, hipStream_t s) {
   using G = TWg<CI, CO, WO>;
   const long items = (long)N * ((H / 2 + G::BRO - 1) / G::BRO);
-  int cus = cu_count();
-  if (cus <= 0) cus = 256;
+  const int cus = launch_cus();
   const int grid = (int)std::max<long>(1, std::min<long>({items, 2L * cus, (long)max_rows}));  // 2 per CU
   hipLaunchKernelGGL((k_trans_wgrad_lds<CI, CO, WO, T>), dim3(grid), dim3(512), G::LDS, s, dy, mask, x, part, N, H);
   ASR_LAUNCH_CHECK("k_trans_wgrad_lds");

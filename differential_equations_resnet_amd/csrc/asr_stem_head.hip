@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "asr_common.h"
+#include "asr_internal.h"
 
 
 namespace asr {
@@ -403,15 +404,13 @@ __global__ __launch_bounds__(256) void k_head_param_grads(const float* __restric
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-constexpr int kMaxSlabsStem = 512;
-
 bool stem_supported(int Cin, int H, int W, int C) {
   const size_t lds = (size_t)(H + 2) * (W + 2) * Cin * 4;
   const size_t red = (size_t)4 * (9 * Cin + 1) * C * 4;
   return (Cin == 1 || Cin == 3) && C % 4 == 0 && C <= 64 && lds <= 64 * 1024 && red <= 64 * 1024;
 }
 
-static int stem_grid(int N) { return std::max(1, std::min(N, kMaxSlabsStem)); }
+static int stem_grid(int N) { return std::max(1, std::min(N, kMaxStemSlabs)); }
 
 template <int CIN, typename Tin, typename Tout>
 static void launch_stem_fwd(const void* img, const float* w1, const float* b1, int N, int H, int W, int C, float mean,

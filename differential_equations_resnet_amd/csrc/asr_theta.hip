@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "asr_common.h"
+#include "asr_internal.h"
 
 namespace asr {
 
@@ -603,11 +604,6 @@ __global__ void k_project(const float* __restrict__ red_groups, int G, long E, c
   if (dw_out && t < E) dw_out[t] = red_at(t);
   if (dbias && t < Cb) dbias[t] = red_at(E + t);
 }
-
-int theta_dst_pair_host(const int32_t* in, long n_theta, int C, int32_t* out);  // (below)
-int theta_to_w_bf16(const float* theta, long theta_stride, int L, int C, const int32_t* w_src, float gamma, void* w,
-                    long w_stride, bool balance, hipStream_t s, const int32_t* theta_dst = nullptr,
-                    long n_theta = 0);  // (below)
 
 }  // namespace asr
 

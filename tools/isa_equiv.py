@@ -1,47 +1,95 @@
 """Do two git revisions compile the product kernels to the same gfx950
-instruction streams?  (A refactor claimed neutral must: round 4's switch
-cleanup 6c75dab compiles every stack kernel bit-identically to f540cc2, the
-measured tree before it.)  Labels are renumbered, comments and directives
-dropped.  usage: python tools/isa_equiv.py REV_A REV_B [source.hip ...]"""
+instruction streams and the same kernel metadata?  (A refactor claimed neutral
+must: round 4's switch cleanup 6c75dab compiles every stack kernel
+bit-identically to f540cc2, the measured tree before it.)  Labels are
+renumbered, comments and directives dropped.  Prints one same/DIFF line per
+kernel (a kernel of one side only is a DIFF) and a summary; exit status 1 on
+any difference.
+usage: python tools/isa_equiv.py REV_A REV_B [source.hip ...]   (default: every product source)"""
 import os
 import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "differential_equations_resnet_amd/csrc"
+SOURCES = ["asr_theta.hip", "asr_block_mfma.hip", "asr_conv_f32.hip", "asr_stem_head.hip", "asr_api.hip",
+           "asr_dist.hip", "asr_deep16.hip", "asr_stages.hip"]
+META = ["vgpr_count", "sgpr_count", "vgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size"]
 
 
 def kernels(asm):
+    """{kernel symbol: [instruction and label lines]}"""
     out = {}
     for f in re.split(r'\n(?=_Z[\w]+:|[A-Za-z_]\w*:\s+; @)', asm):
         name = f.split(':', 1)[0]
         if not name.startswith('_Z') or 's_endpgm' not in f:
             continue  # (data symbols and the metadata that follows them)
-        body = [re.sub(r'\.LBB\d+_\d+', 'L', l.strip()) for l in f.split('\n')[1:]]
+        # (a label's "; in Loop: Header=BBn_m" comment carries the function's index in its file)
+        body = [re.sub(r'\.LBB\d+_\d+', 'L', l.split(';', 1)[0].strip()) for l in f.split('\n')[1:]]
         # (the trailing __hip_cuid_<hash of the source file> symbol is not code)
-        out[name] = [l for l in body if l and not l.startswith((';', '.', '__hip_cuid_'))]
+        out[name] = [l for l in body if l and not l.startswith(('.', '__hip_cuid_'))]
     return out
 
 
-def compile_rev(rev, src, d):
+def kernel_metadata(asm):
+    """{kernel symbol: {META key: value}} from the .amdgpu_metadata notes (as tests/test_isa.py reads them)"""
+    out = {}
+    # (one "  - " entry per kernel, keys sorted: group_segment_fixed_size stands before .name)
+    for entry in re.split(r"\n  - ", asm.split("amdhsa.kernels:", 1)[-1].split(".end_amdgpu_metadata", 1)[0]):
+        name = re.search(r"^    \.name:\s+(\S+)", entry, re.M)
+        if name:
+            vals = {k: re.search(r"^    \." + k + r":\s+(\d+)", entry, re.M) for k in META}
+            out[name.group(1)] = {k: int(v.group(1)) if v else 0 for k, v in vals.items()}
+    return out
+
+
+def compile_tree(tree, src, out):
+    """(kernels, metadata) of tree/CSRC/src, compiled to the assembly file `out`"""
+    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S",
+                    "-w", "-o", out, os.path.join(tree, CSRC, src)], check=True)
+    asm = open(out).read()
+    return kernels(asm), kernel_metadata(asm)
+
+
+def export(rev, d):
     dst = os.path.join(d, rev)
     os.makedirs(dst, exist_ok=True)
     tar = subprocess.run(["git", "-C", ROOT, "archive", rev, CSRC, "include"], check=True, capture_output=True).stdout
     subprocess.run(["tar", "-x", "-C", dst], input=tar, check=True)
-    out = os.path.join(dst, src + ".s")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S",
-                    "-w", "-o", out, os.path.join(dst, CSRC, src)], check=True)
-    return kernels(open(out).read())
+    return dst
+
+
+def compare(tree_a, tree_b, srcs, d):
+    """Print one line per kernel and the summary; the number of differing kernels."""
+    jobs = [(t, s, os.path.join(d, f"{i}_{s}.s")) for s in srcs for i, t in enumerate((tree_a, tree_b))]
+    with ThreadPoolExecutor(min(len(jobs), os.cpu_count() or 1, 16)) as pool:
+        res = list(pool.map(lambda j: compile_tree(*j), jobs))
+    total = diffs = 0
+    for n, src in enumerate(srcs):
+        (ka, ma), (kb, mb) = res[2 * n], res[2 * n + 1]
+        for k in sorted(set(ka) | set(kb)):
+            if k not in ka or k not in kb:
+                tag = "DIFF (only in %s)" % ("A" if k in ka else "B")
+            elif ka[k] != kb[k]:
+                tag = "DIFF (instructions)"
+            elif k not in ma or k not in mb:
+                tag = "DIFF (no metadata entry in %s)" % " and ".join(s for s, m in (("A", ma), ("B", mb)) if k not in m)
+            elif ma[k] != mb[k]:
+                tag = "DIFF (metadata: " + ", ".join(f"{m} {ma[k][m]} -> {mb[k][m]}" for m in META
+                                                     if ma[k][m] != mb[k][m]) + ")"
+            else:
+                tag = "same"
+            total += 1
+            diffs += tag != "same"
+            print(f"{tag} {src} {k[:90]}")
+    print(f"isa_equiv: {total} kernels in {len(srcs)} sources, {total - diffs} same, {diffs} DIFF")
+    return diffs
 
 
 if __name__ == "__main__":
     a, b = sys.argv[1], sys.argv[2]
-    srcs = sys.argv[3:] or ["asr_block_mfma.hip"]
     with tempfile.TemporaryDirectory() as d:
-        for src in srcs:
-            ka, kb = compile_rev(a, src, d), compile_rev(b, src, d)
-            for k in sorted(set(ka) | set(kb)):
-                tag = "same" if ka.get(k) == kb.get(k) else "DIFF"
-                print(f"{tag} {src} {k[:90]}")
+        sys.exit(1 if compare(export(a, d), export(b, d), sys.argv[3:] or SOURCES, d) else 0)
