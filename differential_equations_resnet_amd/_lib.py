@@ -29,7 +29,7 @@ ASR_BF16 = 1
 ASR_PARAM_3BY3 = 0
 ASR_PARAM_GENERAL = 1
 ASR_PARAM_REGULAR = 2
-ABI_VERSION = 8
+ABI_VERSION = 9
 ASR_MODE_EULER = 0
 ASR_MODE_CONV = 1
 ASR_INTEGRATOR_EULER = 0
@@ -99,6 +99,12 @@ SIGNATURES = [
     ("asr_conv_forward_k", _I, [_I, _I, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P]),
     ("asr_conv_backward_workspace_bytes_k", _S, [_I, _I, _I, _I, _I]),
     ("asr_conv_backward_k", _I, [_I, _I, _P, _P, _P, _P, _P, _L, _F, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P, _S, _P]),
+    ("asr_wpack_elems_k", _L, [_I, _I]),
+    ("asr_theta_to_w_k_bf16", _I, [_P, _L, _I, _I, _I, _P, _F, _P, _L, _P]),
+    ("asr_conv_forward_k_bf16", _I, [_I, _I, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P]),
+    ("asr_conv_backward_workspace_bytes_k_bf16", _S, [_I, _I, _I, _I, _I]),
+    ("asr_conv_backward_k_bf16", _I, [_I, _I, _P, _P, _P, _P, _P, _L, _F, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P, _S,
+                                      _P]),
     ("asr_wpack_elems", _L, [_I]),
     ("asr_theta_to_w", _I, [_P, _L, _I, _I, _P, _F, _P, _L, _I, _P]),
     ("asr_conv_forward", _I, [_I, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P]),

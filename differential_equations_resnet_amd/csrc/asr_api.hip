@@ -820,6 +820,77 @@ int asr_conv_backward_k(int mode, int kernel_size, const float* dy, const float*
   return ASR_OK;
 }
 
+// The same layer in bf16 (fp32 accumulation) on the matrix cores (asr_conv_kxk.hip), for
+// kernel_size in {5, 7}, C in {16, 32, 64}, W in {8, 16, 32}; w: asr_theta_to_w_k_bf16's pack.
+static int check_k_bf16(const char* fn, int kernel_size, int W, int C) {
+  if (kernel_size < 1 || kernel_size > 15 || !(kernel_size & 1))
+    return fail(ASR_E_ARG, "%s: kernel_size %d (odd, 1..15)", fn, kernel_size);
+  if (!convk_bf16_supported(kernel_size, W, C))
+    return fail(ASR_E_UNSUPPORTED,
+                "%s: the bf16 k x k kernels take kernel_size in {5, 7}, C in {16, 32, 64}, W in {8, 16, 32} "
+                "(kernel_size=%d C=%d W=%d)", fn, kernel_size, C, W);
+  return ASR_OK;
+}
+
+// workspace of asr_conv_backward_k_bf16: the weight-gradient slabs, then reduce_and_project's rows
+struct BwdWsK {
+  size_t slabs, red, total;
+  int rows;
+};
+static BwdWsK bwd_ws_layout_k_bf16(int N, int H, int W, int C, int K) {
+  BwdWsK b{};
+  const long ES = (long)K * K * C * C + C;
+  b.rows = wgradk_bf16_slab_rows(K, N, H, W, C);
+  b.slabs = 0;
+  b.red = align_up((size_t)b.rows * ES * 4, 256);
+  b.total = b.red + align_up(reduce_ws_bytes(b.rows, ES), 256);
+  return b;
+}
+
+int asr_conv_forward_k_bf16(int mode, int kernel_size, const void* x, void* y, uint8_t* mask, const void* w,
+                            const float* bias, float h, int N, int H, int W, int C, asr_stream_t stream) {
+  ASR_TRY(check_shape(N, H, W, C));
+  if (!x || !y || !w) return fail(ASR_E_ARG, "asr_conv_forward_k_bf16: null pointer");
+  if (mode != ASR_MODE_EULER && mode != ASR_MODE_CONV)
+    return fail(ASR_E_ARG, "asr_conv_forward_k_bf16: bad mode %d", mode);
+  ASR_TRY(check_k_bf16("asr_conv_forward_k_bf16", kernel_size, W, C));
+  return convk_bf16(mode == ASR_MODE_EULER ? F_EULER : F_CONV, kernel_size, x, y, mask, w, bias, h, 0.f, nullptr, N, H,
+                    W, C, (hipStream_t)stream);
+}
+
+size_t asr_conv_backward_workspace_bytes_k_bf16(int N, int H, int W, int C, int kernel_size) {
+  if (check_shape(N, H, W, C) != ASR_OK || !convk_bf16_supported(kernel_size, W, C)) return 0;
+  return bwd_ws_layout_k_bf16(N, H, W, C, kernel_size).total;
+}
+
+int asr_conv_backward_k_bf16(int mode, int kernel_size, const void* dy, const void* x, const uint8_t* mask,
+                             const void* w, const int32_t* theta_dst, long n_theta, float h, float gamma, int N, int H,
+                             int W, int C, void* dx, float* dtheta, float* dbias, float* dw, void* ws, size_t ws_bytes,
+                             asr_stream_t stream) {
+  ASR_TRY(check_shape(N, H, W, C));
+  if (mode != ASR_MODE_EULER && mode != ASR_MODE_CONV)
+    return fail(ASR_E_ARG, "asr_conv_backward_k_bf16: bad mode %d", mode);
+  ASR_TRY(check_k_bf16("asr_conv_backward_k_bf16", kernel_size, W, C));
+  if (!dy || !w || (mode == ASR_MODE_EULER && !mask)) return fail(ASR_E_ARG, "asr_conv_backward_k_bf16: null pointer");
+  if ((dtheta || dbias || dw) && !x) return fail(ASR_E_ARG, "asr_conv_backward_k_bf16: x needed for weight gradients");
+  if (dtheta && !theta_dst) return fail(ASR_E_ARG, "asr_conv_backward_k_bf16: theta_dst needed for dtheta");
+  const BwdWsK Lw = bwd_ws_layout_k_bf16(N, H, W, C, kernel_size);
+  if (!ws || ws_bytes < Lw.total) return fail(ASR_E_WORKSPACE, "asr_conv_backward_k_bf16: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* base = (unsigned char*)ws;
+  const bool euler = mode == ASR_MODE_EULER;
+  if (dx) ASR_TRY(convk_bf16(euler ? B_EULER : B_CONV, kernel_size, dy, dx, nullptr, w, nullptr, h, 2.f * gamma,
+                             euler ? mask : nullptr, N, H, W, C, s));
+  if (dtheta || dbias || dw) {
+    float* slabs = (float*)(base + Lw.slabs);
+    int nsl = 0;
+    ASR_TRY(wgradk_bf16(kernel_size, x, dy, euler ? mask : nullptr, euler ? h : 1.f, N, H, W, C, slabs, &nsl, s));
+    ASR_TRY(reduce_and_project(slabs, nsl, (long)kernel_size * kernel_size * C * C, C, dtheta ? theta_dst : nullptr,
+                               n_theta, dtheta, dbias, dw, (float*)(base + Lw.red), s));
+  }
+  return ASR_OK;
+}
+
 size_t asr_conv_backward_workspace_bytes(int N, int H, int W, int C, int dtype) {
   if (check_shape(N, H, W, C) != ASR_OK) return 0;
   return bwd_ws_layout(N, H, W, C, dtype).total;

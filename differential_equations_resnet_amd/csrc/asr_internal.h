@@ -144,6 +144,15 @@ int wgradb_layers(const void* x0, long x_stride, const void* dys, long d_stride,
                   long mask_stride, float h, int N, int H, int W, int C, int L, float* slabs, long slab_stride,
                   int* nslabs, hipStream_t s);
 
+// ---- asr_conv_kxk.hip ------------------------------------------------------
+// bf16 Conv2DAntisymmetric(kernel_size = K), K in {5, 7}, C in {16, 32, 64}, W in {32, 16, 8}
+bool convk_bf16_supported(int K, int W, int C);
+int convk_bf16(int fmode, int K, const void* xin, void* out, uint8_t* mask, const void* w, const float* bias, float h,
+               float two_gamma, const uint8_t* dmask, int N, int H, int W, int C, hipStream_t s);
+int wgradk_bf16_slab_rows(int K, int N, int H, int W, int C);
+int wgradk_bf16(int K, const void* x, const void* dy, const uint8_t* mask, float h, int N, int H, int W, int C,
+                float* slabs, int* nslabs, hipStream_t s);
+
 // ---- asr_deep16.hip --------------------------------------------------------
 // the C = 16, 32 x 32 bf16 stage as one fused forward / backward launch
 bool deep16_supported(int H, int W, int C);

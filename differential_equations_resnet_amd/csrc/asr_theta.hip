@@ -269,6 +269,38 @@ __global__ void k_theta_to_w_pack(const float* __restrict__ theta, long theta_st
   *(bf16x8*)(w + l * w_stride + ((long)frag * 64 + lane) * 8) = v;
 }
 
+// The same pack for a k x k kernel (taps = k*k: kappa = tap*C + i, tap = ky*k + kx, zero for
+// kappa >= taps*C; KS = ceil(taps*C / 32)), the bf16 W of asr_conv_kxk.hip.  Round to nearest
+// even: it commutes with negation and with the flip / transpose permutation, so the pack of an
+// antisymmetric map stays exactly antisymmetric off the diagonal and the pack of
+// asr_param_map_transpose_k's map is bit for bit -flip(W)^T of the forward pack.  (The balanced
+// rounding below removes an error that only a deep stack sees; nothing stacks k != 3 layers.)
+__global__ void k_theta_to_w_pack_k(const float* __restrict__ theta, long theta_stride, int C, int taps,
+                                    const int32_t* __restrict__ w_src, float gamma, bf16* __restrict__ w,
+                                    long w_stride) {
+  const int KS = (taps * C + 31) / 32;
+  const int OT = C / 16;
+  const int l = blockIdx.y;
+  const int frag = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+  if (frag >= OT * KS) return;
+  const int lane = threadIdx.x & 63;
+  const int ot = frag / KS, ks = frag % KS;
+  const int o = 16 * ot + (lane & 15);
+  const float* th = theta + l * theta_stride;
+  bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int kappa = 32 * ks + 8 * (lane >> 4) + j;
+    float x = 0.f;
+    if (kappa < taps * C) {
+      const int tap = kappa / C, i = kappa % C;
+      x = w_value(th, w_src, ((long)tap * C + i) * C + o, gamma);
+    }
+    v[j] = (bf16)x;
+  }
+  *(bf16x8*)(w + l * w_stride + ((long)frag * 64 + lane) * 8) = v;
+}
+
 // Balanced rounding of the bf16 pack (C in {16, 32, 64}).
 // Rounding W to nearest perturbs output channel o by the fixed sum of its
 // row's rounding errors, which every pixel of every image and every layer of a
@@ -612,7 +644,7 @@ using namespace asr;
 extern "C" {
 
 const char* asr_last_error(void) { return g_err; }
-int asr_abi_version(void) { return 8; }
+int asr_abi_version(void) { return 9; }
 
 int asr_device_cu_count(void) { return cu_count(); }
 
@@ -658,6 +690,29 @@ int asr_theta_to_w_k(const float* theta, long theta_stride, int L, int C, int ke
   hipLaunchKernelGGL(k_theta_to_w_hwio, grid, dim3(256), 0, (hipStream_t)stream, theta, theta_stride, E, w_src, gamma,
                      w_out, w_stride);
   ASR_LAUNCH_CHECK("k_theta_to_w_hwio");
+  return ASR_OK;
+}
+
+long asr_wpack_elems_k(int C, int kernel_size) {
+  if ((kernel_size != 5 && kernel_size != 7) || (C != 16 && C != 32 && C != 64)) return -1;
+  return (long)(C / 16) * ((kernel_size * kernel_size * C + 31) / 32) * 64 * 8;
+}
+
+int asr_theta_to_w_k_bf16(const float* theta, long theta_stride, int L, int C, int kernel_size, const int32_t* w_src,
+                          float gamma, void* w_pack, long w_stride, asr_stream_t stream) {
+  if (!theta || !w_src || !w_pack || L < 1 || C < 1 || L > 65535 || kernel_size < 1 || kernel_size > 15 ||
+      !(kernel_size & 1))
+    return fail(ASR_E_ARG, "asr_theta_to_w_k_bf16: bad arguments");
+  const long n = asr_wpack_elems_k(C, kernel_size);
+  if (n < 0)
+    return fail(ASR_E_UNSUPPORTED,
+                "asr_theta_to_w_k_bf16: the bf16 k x k kernels take kernel_size in {5, 7}, C in {16, 32, 64}, "
+                "W in {8, 16, 32} (kernel_size=%d C=%d)", kernel_size, C);
+  if (w_stride < n) return fail(ASR_E_ARG, "asr_theta_to_w_k_bf16: w_stride too small");
+  const int frags = (int)(n / 512);
+  hipLaunchKernelGGL(k_theta_to_w_pack_k, dim3((frags + 3) / 4, L), dim3(256), 0, (hipStream_t)stream, theta,
+                     theta_stride, C, kernel_size * kernel_size, w_src, gamma, (bf16*)w_pack, w_stride);
+  ASR_LAUNCH_CHECK("k_theta_to_w_pack_k");
   return ASR_OK;
 }
 

@@ -72,7 +72,10 @@ class AntisymmetricConvBase(Layer):
         if k < 1 or k % 2 == 0 or k > 15:
             raise _lib.AsrUnsupported(f"{self.name}: kernel_size {k} (odd 1..15 have native kernels)")
         if k != 3 and dtype is not None and str(dtype) != "torch.float32":
-            raise _lib.AsrUnsupported(f"{self.name}: kernel_size {k} runs the fp32 k x k kernels (input {dtype})")
+            # bf16: the matrix-core k x k kernels (runtime checks C and W of their supported set)
+            if str(dtype) != "torch.bfloat16" or k not in (5, 7):
+                raise _lib.AsrUnsupported(f"{self.name}: kernel_size {k} runs the fp32 k x k kernels, and the bf16 "
+                                          f"ones for kernel_size 5 and 7 (input {dtype})")
 
     def param_map(self):
         from .. import runtime

@@ -139,6 +139,22 @@ def wpack_elems(C: int) -> int:
     return int(n)
 
 
+KXK_BF16 = "kernel_size in {5, 7}, C in {16, 32, 64}, W in {8, 16, 32}"
+
+
+def wpack_elems_k(C: int, k: int) -> int:
+    """Elements of one layer's packed bf16 k x k W (asr_wpack_elems_k)."""
+    n = _lib.load().asr_wpack_elems_k(C, k)
+    if n < 0:
+        raise _lib.AsrUnsupported(f"kernel_size {k}, C={C}: the bf16 k x k kernels take {KXK_BF16}")
+    return int(n)
+
+
+def _check_kxk_bf16(k: int, C: int, W: int):
+    if k not in (5, 7) or C not in (16, 32, 64) or W not in (8, 16, 32):
+        raise _lib.AsrUnsupported(f"kernel_size {k}, C={C}, W={W}: the bf16 k x k kernels take {KXK_BF16}")
+
+
 def theta_to_w(theta: torch.Tensor, C: int, pmap: ParamMap, gamma: float, dtype: int, layers: int = 1,
                theta_stride: int | None = None) -> torch.Tensor:
     """Materialise W for `layers` layers whose thetas are theta_stride floats
@@ -146,9 +162,13 @@ def theta_to_w(theta: torch.Tensor, C: int, pmap: ParamMap, gamma: float, dtype:
     dev = theta.device
     w_src, _ = pmap.device(dev)
     stride = pmap.n_theta if theta_stride is None else theta_stride
-    if pmap.k != 3:  # Conv2DAntisymmetric(kernel_size != 3): fp32 HWIO only
-        if dtype != ASR_F32:
-            raise _lib.AsrUnsupported(f"kernel_size {pmap.k}: the k x k kernels are fp32")
+    if pmap.k != 3:  # Conv2DAntisymmetric(kernel_size != 3): fp32 HWIO, or the bf16 pack for k in {5, 7}
+        if dtype == ASR_BF16:
+            per = wpack_elems_k(C, pmap.k)
+            out = torch.empty(layers * per, dtype=torch.bfloat16, device=dev)
+            _lib.call("asr_theta_to_w_k_bf16", _p(theta), stride, layers, C, pmap.k, _p(w_src), float(gamma), _p(out),
+                      per, _stream())
+            return out.view(layers, per)
         per = pmap.k * pmap.k * C * C
         out = torch.empty(layers * per, dtype=torch.float32, device=dev)
         _lib.call("asr_theta_to_w_k", _p(theta), stride, layers, C, pmap.k, _p(w_src), float(gamma), _p(out), per,
@@ -172,8 +192,12 @@ def theta_to_w_transposed(theta: torch.Tensor, C: int, pmap: ParamMap, dtype: in
     dev = theta.device
     wb = pmap.w_src_bwd(dev)
     if pmap.k != 3:
-        if dtype != ASR_F32:
-            raise _lib.AsrUnsupported(f"kernel_size {pmap.k}: the k x k kernels are fp32")
+        if dtype == ASR_BF16:
+            per = wpack_elems_k(C, pmap.k)
+            out = torch.empty(per, dtype=torch.bfloat16, device=dev)
+            _lib.call("asr_theta_to_w_k_bf16", _p(theta), pmap.n_theta, 1, C, pmap.k, _p(wb), 0.0, _p(out), per,
+                      _stream())
+            return out.view(1, per)
         per = pmap.k * pmap.k * C * C
         out = torch.empty(per, dtype=torch.float32, device=dev)
         _lib.call("asr_theta_to_w_k", _p(theta), pmap.n_theta, 1, C, pmap.k, _p(wb), 0.0, _p(out), per, _stream())
@@ -216,9 +240,12 @@ def conv_forward(mode: int, x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor
     if not x.is_contiguous():
         raise ValueError("x must be contiguous NHWC")
     y = torch.empty_like(x)
+    if k != 3 and dt == ASR_BF16:
+        _check_kxk_bf16(k, C, W)
+        _lib.call("asr_conv_forward_k_bf16", mode, k, _p(x), _p(y), _p(mask), _p(w), _p(bias), float(h), N, H, W, C,
+                  _stream())
+        return y
     if k != 3:
-        if dt != ASR_F32:
-            raise _lib.AsrUnsupported(f"kernel_size {k}: the k x k kernels are fp32")
         _lib.call("asr_conv_forward_k", mode, k, _p(x), _p(y), _p(mask), _p(w), _p(bias), float(h), N, H, W, C,
                   _stream())
         return y
@@ -281,9 +308,11 @@ def conv_backward(mode: int, dy: torch.Tensor, x: torch.Tensor, mask: torch.Tens
     dt = dtype_code(dy.dtype)
     dev = dy.device
     k = pmap.k
-    if k != 3 and dt != ASR_F32:
-        raise _lib.AsrUnsupported(f"kernel_size {k}: the k x k kernels are fp32")
-    if k != 3:
+    kbf = k != 3 and dt == ASR_BF16
+    if kbf:
+        _check_kxk_bf16(k, C, W)
+        ws_bytes = int(_lib.load().asr_conv_backward_workspace_bytes_k_bf16(N, H, W, C, k))
+    elif k != 3:
         ws_bytes = int(_lib.load().asr_conv_backward_workspace_bytes_k(N, H, W, C, k))
     else:
         ws_bytes = int(_lib.load().asr_conv_backward_workspace_bytes(N, H, W, C, dt))
@@ -294,8 +323,9 @@ def conv_backward(mode: int, dy: torch.Tensor, x: torch.Tensor, mask: torch.Tens
     dw = torch.empty(k, k, C, C, dtype=torch.float32, device=dev) if want_dw else None
     _, theta_dst = pmap.device(dev)
     if k != 3:
-        _lib.call("asr_conv_backward_k", mode, k, _p(dy), _p(x), _p(mask), _p(w), _p(theta_dst), pmap.n_theta,
-                  float(h), float(gamma), N, H, W, C, _p(dx), _p(dth), _p(db), _p(dw), _p(ws), ws_bytes, _stream())
+        _lib.call("asr_conv_backward_k_bf16" if kbf else "asr_conv_backward_k", mode, k, _p(dy), _p(x), _p(mask),
+                  _p(w), _p(theta_dst), pmap.n_theta, float(h), float(gamma), N, H, W, C, _p(dx), _p(dth), _p(db),
+                  _p(dw), _p(ws), ws_bytes, _stream())
         return dx, dth, db, dw
     _lib.call("asr_conv_backward", mode, _p(dy), _p(x), _p(mask), _p(w), _p(theta_dst), pmap.n_theta, float(h),
               float(gamma), N, H, W, C, dt, _p(dx), _p(dth), _p(db), _p(dw), _p(ws), ws_bytes, _stream())

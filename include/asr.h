@@ -200,8 +200,8 @@ int asr_conv_backward(int mode, const void* dy, const void* x, const uint8_t* ma
  * Conv2DAntisymmetric(kernel_size = k) for odd k != 3
  * (layers/tfkeras_layer_Conv2DAntisymmetric.py:60-68, 109-145, 163-170):
  * the same operator family on a k x k kernel (k = 3 is the functions above).
- * fp32 (the reference's precision); W HWIO [k,k,C,C]; maps of k*k*C*C
- * entries.  The antisymmetric kinds keep A^T = -A + 2 gamma I, so
+ * fp32 (the reference's precision; bf16 for k = 5 and 7: the next section);
+ * W HWIO [k,k,C,C]; maps of k*k*C*C entries.  The antisymmetric kinds keep A^T = -A + 2 gamma I, so
  * asr_conv_backward_k takes the forward W (else W_bwd of
  * asr_param_map_transpose_k with gamma 0), as asr_conv_backward.
  * ---------------------------------------------------------------------- */
@@ -217,6 +217,45 @@ int asr_conv_backward_k(int mode, int kernel_size, const float* dy, const float*
                         const float* w, const int32_t* theta_dst, long n_theta, float h, float gamma, int N, int H,
                         int W, int C, float* dx, float* dtheta, float* dbias, float* dw, void* ws, size_t ws_bytes,
                         asr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * The same layer in bf16 (ABI 9): bf16 activations and W, fp32 accumulation,
+ * on v_mfma_f32_16x16x32_bf16, both modes, forward and backward.
+ * Supported set: kernel_size in {5, 7}, C in {16, 32, 64}, W in {8, 16, 32},
+ * any H >= 1 and N >= 1; every other odd kernel_size 1..15 or shape returns
+ * ASR_E_UNSUPPORTED (use the fp32 functions above).
+ *   asr_wpack_elems_k: elements of one layer's packed W, (C/16)*KS*512 with
+ *     KS = ceil(k*k*C / 32); < 0 outside the supported set.
+ *   asr_theta_to_w_k_bf16: the 3x3 pack's layout with 9 replaced by k*k: the
+ *     element of output channel o and reduction index kappa = tap*C + i
+ *     (tap = ky*k + kx) sits at
+ *       (((o/16)*KS + kappa/32)*64 + o%16 + 16*((kappa%32)/8))*8 + kappa%8,
+ *     zero for kappa >= k*k*C; layer l at w_pack + l*w_stride elements.
+ *     Rounded to nearest even (not the 3x3 pack's balanced rounding), so an
+ *     antisymmetric W stays exactly antisymmetric off the diagonal and the
+ *     pack of asr_param_map_transpose_k's map is bit for bit -flip(W)^T of
+ *     the forward pack.
+ *   asr_conv_forward_k_bf16 / asr_conv_backward_k_bf16: as the fp32 pair, x /
+ *     y / dy / dx bf16 [N,H,W,C], w one layer's pack, mask in the layout of
+ *     asr_conv_forward.  EULER's dz = h*(dy & mask): the mask is applied to the
+ *     bf16 dy exactly and h in fp32 (the weight gradients' sums, the dx terms).
+ *     dw (may be NULL) receives the unprojected dW, float [k][k][C][C].
+ *   asr_conv_backward_workspace_bytes_k_bf16: weight-gradient slabs of
+ *     k*k*C*C + C floats and their reduction rows; the slab count is bounded by
+ *     48 MB of slabs and by 256, so the workspace stays <= 64 MB for every
+ *     supported shape (49.8 MB at k = 7, C = 64: 59 slabs of 803 KB); 0
+ *     outside the supported set.
+ * ---------------------------------------------------------------------- */
+long asr_wpack_elems_k(int C, int kernel_size);
+int asr_theta_to_w_k_bf16(const float* theta, long theta_stride, int L, int C, int kernel_size, const int32_t* w_src,
+                          float gamma, void* w_pack, long w_stride, asr_stream_t stream);
+int asr_conv_forward_k_bf16(int mode, int kernel_size, const void* x, void* y, uint8_t* mask, const void* w,
+                            const float* bias, float h, int N, int H, int W, int C, asr_stream_t stream);
+size_t asr_conv_backward_workspace_bytes_k_bf16(int N, int H, int W, int C, int kernel_size);
+int asr_conv_backward_k_bf16(int mode, int kernel_size, const void* dy, const void* x, const uint8_t* mask,
+                             const void* w, const int32_t* theta_dst, long n_theta, float h, float gamma, int N, int H,
+                             int W, int C, void* dx, float* dtheta, float* dbias, float* dw, void* ws, size_t ws_bytes,
+                             asr_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * RK2 (explicit midpoint) block — an EXTENSION, not in the reference
