@@ -129,7 +129,11 @@ __global__ __launch_bounds__(256) void k_stem_fwd(const Tin* __restrict__ img, c
 // Thread = (4-channel group cg, pixel lane); the normalised image tile in
 // LDS, one broadcast LDS read per tap feeds 4 channels (packed FMAs).  The
 // pixel lanes of a wave reduce by shuffles, the 4 waves through LDS (fixed
-// order: deterministic).  C % 4 == 0 and C <= 64.
+// order: deterministic).  C % 4 == 0 and C <= 64.  A pixel lane holds NGP
+// threads, C/4 rounded up to a power of two, so that a pixel lane never
+// straddles a wave and the xor butterfly stays within one channel group; the
+// NGP - C/4 surplus threads of a lane (C = 12, 20, 24, 28, 36 .. 60) touch no
+// memory and carry zeros through the reduction.
 template <int CIN, typename Tin, typename T>
 __global__ __launch_bounds__(256) void k_stem_wgrad(const Tin* __restrict__ img, const T* __restrict__ dx1,
                                                     const T* __restrict__ x1, int N, int H, int W, int C, float mean,
@@ -137,9 +141,12 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(const Tin* __restrict__ img,
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int KC = 9 * CIN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int NG = C / 4;     // channel groups (<= 16)
-  const int PL = 256 / NG;  // pixel lanes
-  const int cg = tid % NG, pl = tid / NG;
+  const int NG = C / 4;  // channel groups (<= 16)
+  int NGP = 1;           // threads per pixel lane: a power of two (divides 64)
+  while (NGP < NG) NGP <<= 1;
+  const int PL = 256 / NGP;  // pixel lanes
+  const int cg = tid % NGP, pl = tid / NGP;
+  const int HWa = cg < NG ? H * W : 0;  // a surplus thread takes no pixels
   f32x2 acc[KC + 1][2];
 #pragma unroll
   for (int k = 0; k <= KC; ++k) acc[k][0] = acc[k][1] = f32x2{0.f, 0.f};
@@ -153,7 +160,7 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(const Tin* __restrict__ img,
     const T* d = dx1 + (long)n * H * W * C + cg * 4;
     const T* a = x1 + (long)n * H * W * C + cg * 4;
     constexpr int U = 4;  // pixels per batch: all global loads issued before use
-    for (int p0 = pl; p0 < H * W; p0 += U * PL) {
+    for (int p0 = pl; p0 < HWa; p0 += U * PL) {
       f32x2 gv[U][2];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -196,7 +203,7 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(const Tin* __restrict__ img,
       }
     }
   }
-  // pixel lanes of this wave: lanes cg, cg+NG, ... (NG divides 64)
+  // pixel lanes of this wave: lanes cg, cg+NGP, ... (NGP, a power of two <= 16, divides 64)
 #pragma unroll
   for (int k = 0; k <= KC; ++k)
 #pragma unroll
@@ -204,12 +211,12 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(const Tin* __restrict__ img,
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
         float v = acc[k][h][e];
-        for (int off = NG; off < 64; off <<= 1) v += __shfl_xor(v, off);
+        for (int off = NGP; off < 64; off <<= 1) v += __shfl_xor(v, off);
         acc[k][h][e] = v;
       }
   __syncthreads();
   float* red = sm;  // [4 waves][KC+1][C]
-  if (lane < NG)
+  if (lane < NG)  // (lane < NGP: cg == lane)
 #pragma unroll
     for (int k = 0; k <= KC; ++k)
 #pragma unroll
@@ -309,7 +316,8 @@ __global__ __launch_bounds__(256) void k_head(const T* __restrict__ xL, const fl
         const float qv = lg[k] / s2;
         const float qc = fminf(fmaxf(qv, eps), 1.f - eps);
         const float t = targets[(long)n * K + k];
-        loss -= t * logf(qc);
+        // clipped from above (qv = 1): -log(1 - 1e-7) = 1e-7; the float 1.f - eps is 1 - 2^-23, whose log is 19 % larger
+        loss -= t * (qv > 1.f - eps ? -eps : logf(qc));
         const float dq = (qv >= eps && qv <= 1.f - eps) ? -t / qc * inv_n : 0.f;
         dl[k] = dq;
         sdq_p += dq * lg[k];

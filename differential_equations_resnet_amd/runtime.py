@@ -216,6 +216,8 @@ def segment_sq_norms(x: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
     """out[i] = sum(x[offsets[i]:offsets[i+1]]**2) (asr_segment_sq_norms)."""
     n = offsets.numel() - 1
     out = torch.empty(n, dtype=torch.float32, device=x.device)
+    if n <= 0:  # (an empty tensor has no address to pass)
+        return out
     _lib.call("asr_segment_sq_norms", _p(x), _p(offsets), n, _p(out), _stream())
     return out
 
@@ -434,7 +436,8 @@ class NetExecutor:
         lib = _lib.load()
         with torch.cuda.device(self.device):  # the layout (slab rows) follows the device's CU count
             self.n_params = int(lib.asr_net_param_count(ct.byref(self.cfg)))
-            if self.n_params < 0:
+            if self.n_params < 0:  # the config check's own code (ASR_E_ARG or ASR_E_UNSUPPORTED), before any launch
+                _lib.call("asr_net_prepare", ct.byref(self.cfg), None, 0)
                 _lib.check(_lib.ASR_E_ARG, "asr_net_param_count")
             self.ws_bytes = int(lib.asr_net_workspace_bytes(ct.byref(self.cfg)))
             if self.ws_bytes == 0:

@@ -313,6 +313,8 @@ int asr_rk2_stack_backward(const void* dyL, const void* xs, const void* xmids, l
  *   conv1 kernel [3,3,Cin,C], conv1 bias [C],
  *   L x (theta [asr_theta_count(C, param_kind, antisymmetric)], bias [C]),
  *   fc kernel [C,K], fc bias [K].
+ * C and num_classes above 256 return ASR_E_UNSUPPORTED (the head runs one
+ * 256-thread workgroup per image), as asr_stages_check does.
  * --------------------------------------------------------------------- */
 typedef struct asr_net_config {
   int N, H, W, Cin, C, L, num_classes;

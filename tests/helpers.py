@@ -155,6 +155,87 @@ def assert_grad_tensors_max(spec, got, want, tol, report_only=False, groups=None
     return worst
 
 
+CLIP_BAND = (1e-8, 1e-6)  # no renormalised q or 1 - q of a clip case may lie here (Keras' epsilon is 1e-7)
+
+
+def clip_case(seed=0):
+    """A batch that exercises Keras' probability clip in the head (k_head):
+    (spec, params, images float32, onehot).  fp32 net, float images, no
+    input normalisation, L=1, fc bias (+24, -24, 0, ...).  Conv1's channel 0
+    has an all-positive kernel, so the pooled feature 0 measures brightness;
+    fc row 0 is -bias / (feature 0 of a bright image).  The 4 bright images'
+    logits are therefore O(1) (unsaturated), the 8 dim images' logits are the
+    bias: true class 0 there has probability > 1 - 1e-9, any other true class
+    < 1e-9.  clip_classes() says which image is which; test_clip_case_is_
+    conditioned (CPU) asserts the margins."""
+    from oracle import asr_oracle as O
+    rng = np.random.default_rng(seed)
+    K, C, N = 10, 16, 12
+    spec = O.NetSpec(C=C, L=1, h=0.5, gamma=0.0, num_classes=K, H=6, W=7, Cin=3, subtract_mean=None,
+                     divide_by_stddev=None)
+    params = O.init_params(spec, rng, np.float64, bias_std=0.05)
+    params[0][..., 0] = np.abs(params[0][..., 0])
+    params[1][0] = 0.0
+    imgs = rng.uniform(0.5, 1.0, (N, spec.H, spec.W, 3)).astype(np.float32)
+    imgs[4:] *= np.float32(0.01)
+    bias = np.zeros(K)
+    bias[0], bias[1] = 24.0, -24.0
+    params[-1] = bias
+    params[-2] = params[-2] * 0.05
+    params = [p.astype(np.float32).astype(np.float64) for p in params]
+    _, cache = O.net_forward(spec, params, imgs)
+    gbar = cache["gap"][:4, 0].mean()
+    params[-2][0] = (-bias / gbar).astype(np.float32).astype(np.float64)
+    labels = np.array([0, 1, 5, 9, 0, 0, 0, 1, 1, 4, 7, 9])
+    return spec, params, imgs, np.eye(K)[labels]
+
+
+def clip_classes(probs, onehot):
+    """(low, high, unsaturated) boolean masks over the images, from fp64
+    probabilities: true-class renormalised q < 1e-9, 1 - q < 1e-9, or
+    1e-6 < q < 1 - 1e-6; and the smallest distance factor of any q or 1 - q
+    to CLIP_BAND as a bool `clear` (True: nothing inside the band)."""
+    q = probs / probs.sum(axis=-1, keepdims=True)
+    qt = (q * onehot).sum(axis=-1)
+    omt = ((1.0 - q) * onehot).sum(axis=-1)
+    lo, hi = CLIP_BAND
+    clear = not (((q >= lo) & (q <= hi)).any() or ((1.0 - q >= lo) & (1.0 - q <= hi)).any())
+    return qt < 1e-9, omt < 1e-9, (qt > hi) & (omt > hi), clear
+
+
+def metrics_case(N, K, seed=0):
+    """One batch for asr_batch_metrics: (probs float32 [N, K], onehot float32).
+    Rows that do not sum to 1 (scaled by 0.7 / 1.3: renormalisation), entries
+    of 1e-9 (below the clip, on the true class in every 7th row), and in
+    every 3rd row an exactly tied maximum at the index pairs (0, 3) and
+    (2, K-1) alternately ((0, K-1) where K < 4), the target on the first
+    index in one tied row and on the second in the next: the count must
+    follow np.argmax (first maximum).  tie_rows() lists the tied rows."""
+    rng = np.random.default_rng(seed)
+    p = rng.uniform(0.05, 1.0, (N, K))
+    p /= p.sum(axis=-1, keepdims=True)
+    labels = rng.integers(0, K, N)
+    p *= np.where(np.arange(N) % 4 == 1, 0.7, np.where(np.arange(N) % 4 == 2, 1.3, 1.0))[:, None]
+    p = p.astype(np.float32)
+    for r, i, j in tie_rows(N, K):
+        p[r, i] = p[r, j] = np.float32(2.0) * p[r].max()
+        labels[r] = i if (r // 3) % 4 < 2 else j
+    for r in range(1, N, 7):  # (rows r % 3 == 0 are the tied ones)
+        if r % 3:
+            p[r, labels[r]] = np.float32(1e-9)
+        if (r + 2) % 3 and K > 1 and r + 2 < N:
+            p[r + 2, (labels[r + 2] + 1) % K] = np.float32(1e-9)
+    return p, np.eye(K, dtype=np.float32)[labels]
+
+
+def tie_rows(N, K):
+    """[(row, i, j)]: rows of metrics_case whose maximum is tied at i < j."""
+    if K < 2:
+        return []
+    pairs = [(0, 3), (2, K - 1)] if K >= 4 else [(0, K - 1)]
+    return [(r, *pairs[(r // 3) % len(pairs)]) for r in range(0, N, 3)]
+
+
 def assert_grad_groups_rel_l2(spec, got, want, tol=2e-2):
     """bf16 network gradients vs the fp64 oracle: relative L2 <= tol per
     gradient group."""
