@@ -572,6 +572,27 @@ int asr_conv_forward(int mode, const void* x, void* y, uint8_t* mask, const void
   return fail(ASR_E_ARG, "asr_conv_forward: bad dtype %d", dtype);
 }
 
+// the image-resident stage kernels (k_stagef / k_stageb, k_stagef32 / k_stageb32) behind the stack ABI
+static bool stack_img_supported(int H, int W, int C, int dtype) {
+  return dtype == ASR_BF16 ? stage_img_supported(H, W, C) : dtype == ASR_F32 && stage_img32_supported(H, W, C);
+}
+
+// Their vector accesses need per-layer strides that keep every layer aligned
+// (a stride of 0 means "not passed to this call").  bf16: 8-B y stores, 2-B
+// mask stores, 16-B W fragment / bias / x (k_wgradb) loads; fp32: 16-B y
+// stores and bias / x (k_wgrad32) loads, 2-B mask stores, scalar W loads.
+static int stack_img_check_strides(const char* who, int dtype, long y_stride, long mask_stride, long w_stride,
+                                   long bias_stride, long x_stride) {
+  const bool bf = dtype == ASR_BF16;
+  if (y_stride % 4) return fail(ASR_E_ARG, "%s: y_stride %% 4 != 0 on the image-resident path", who);
+  if (mask_stride % 2) return fail(ASR_E_ARG, "%s: mask_stride %% 2 != 0 on the image-resident path", who);
+  if (bf && w_stride % 8) return fail(ASR_E_ARG, "%s: w_stride %% 8 != 0 on the image-resident path", who);
+  if (bias_stride % 4) return fail(ASR_E_ARG, "%s: bias_stride %% 4 != 0 on the image-resident path", who);
+  if (x_stride % (bf ? 8 : 4))
+    return fail(ASR_E_ARG, "%s: x_stride %% %d != 0 on the image-resident path", who, bf ? 8 : 4);
+  return ASR_OK;
+}
+
 int asr_block_stack_forward(const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride, const void* w,
                             long w_stride, const float* bias, long bias_stride, float h, int N, int H, int W, int C,
                             int L, int dtype, int store_all, asr_stream_t stream) {
@@ -585,11 +606,21 @@ int asr_block_stack_forward(const void* x0, void* ys, long y_stride, uint8_t* ma
       return fail(ASR_E_ARG, "asr_block_stack_forward: w_stride must be asr_wpack_elems(C) on the fused path");
     return deep16_forward(x0, ys, y_stride, masks, mask_stride, w, bias, bias_stride, h, N, L, store_all != 0, s);
   }
-  if (dtype == ASR_BF16 && !mfma_supported(C, W))
-    return fail(ASR_E_UNSUPPORTED, "bf16 conv needs C in {16,32,64} and W == 32 (C=%d W=%d)", C, W);
+  if (dtype == ASR_BF16 && !mfma_supported(C, W) && !convb_supported(W, C))
+    return fail(ASR_E_UNSUPPORTED, "bf16 conv needs C in {16,32,64} and W in {32, 16, 8} (C=%d W=%d)", C, W);
   if (dtype != ASR_F32 && dtype != ASR_BF16) return fail(ASR_E_ARG, "asr_block_stack_forward: bad dtype");
   const size_t es = dtype == ASR_BF16 ? 2 : 4;
   if (!store_all && L > 1) return fail(ASR_E_UNSUPPORTED, "asr_block_stack_forward: store_all=0 needs the fused path");
+  // image-resident stages: all L blocks in one launch, a workgroup per image.  The kernels store every
+  // layer and read bias and masks unconditionally; calls without them take the per-block sequence.
+  if (stack_img_supported(H, W, C, dtype) && store_all && bias && masks) {
+    ASR_TRY(stack_img_check_strides("asr_block_stack_forward", dtype, y_stride, mask_stride, w_stride, bias_stride, 0));
+    if (dtype == ASR_BF16)
+      return stage_img_forward(x0, ys, y_stride, masks, mask_stride, w, w_stride, bias, bias_stride, h, N, H, W, C, L,
+                               s);
+    return stage_img32_forward((const float*)x0, (float*)ys, y_stride, masks, mask_stride, (const float*)w, w_stride,
+                               bias, bias_stride, h, N, H, W, C, L, s);
+  }
   if (dtype == ASR_BF16 && block_stack_fwd_supported(N, H, W, C))
     return block_stack_fwd_mfma(x0, ys, L > 1 ? y_stride : (long)N * H * W * C, masks, mask_stride, w, w_stride, bias,
                                 bias_stride, h, N, H, W, C, L, s);
@@ -606,9 +637,10 @@ int asr_block_stack_forward(const void* x0, void* ys, long y_stride, uint8_t* ma
 // workspace of asr_block_stack_backward: two dx buffers, then either the
 // fused path's slabs + group rows or one per-block backward workspace
 struct StackWs {
-  size_t da, db, slabs, grp, blk, done, tdst, g, total;
-  bool deep, stack64;
+  size_t da, db, slabs, grp, blk, done, tdst, g, dys, total;
+  bool deep, stack64, img;
   int grid;
+  int rows;  // img: slab rows per layer (f32_block_slab_rows)
 };
 static StackWs stack_ws_layout(int N, int H, int W, int C, int L, int dtype, bool rk2 = false) {
   StackWs w{};
@@ -617,12 +649,21 @@ static StackWs stack_ws_layout(int N, int H, int W, int C, int L, int dtype, boo
   w.deep = !rk2 && dtype == ASR_BF16 && deep16_supported(H, W, C);
   w.stack64 = dtype == ASR_BF16 && !w.deep && block_stack_bwd_supported(N, H, W, C);
   w.grid = w.stack64 ? block_stack_bwd_grid(N) : 0;
+  w.img = !rk2 && !w.deep && !w.stack64 && stack_img_supported(H, W, C, dtype);
   size_t off = 0;
   w.da = off;
   off += act;
   w.db = off;
   off += act;
-  if (w.deep) {
+  if (w.img) {  // the gradient entering every layer (L activations, unpadded), slabs [L][rows][ES], group rows
+    w.rows = f32_block_slab_rows(N, H, W, C);
+    w.dys = off;
+    off += align_up((size_t)L * N * H * W * C * (dtype == ASR_BF16 ? 2 : 4), 256);
+    w.slabs = off;
+    off += align_up((size_t)L * w.rows * ES * 4, 256);
+    w.grp = off;
+    off += align_up((size_t)L * reduce_groups(w.rows) * ES * 4, 256);
+  } else if (w.deep) {
     w.slabs = off;
     off += align_up(deep16_slab_bytes(N, L), 256);
     w.grp = off;
@@ -661,14 +702,38 @@ int asr_block_stack_backward(const void* dyL, const void* xs, long x_stride, con
   if (!dyL || !xs || !masks || !w || !dx0 || L < 1) return fail(ASR_E_ARG, "asr_block_stack_backward: null pointer");
   if (dparams && !theta_dst) return fail(ASR_E_ARG, "asr_block_stack_backward: theta_dst needed for dparams");
   if (dtype != ASR_F32 && dtype != ASR_BF16) return fail(ASR_E_ARG, "asr_block_stack_backward: bad dtype");
-  if (dtype == ASR_BF16 && !mfma_supported(C, W))
-    return fail(ASR_E_UNSUPPORTED, "bf16 conv needs C in {16,32,64} and W == 32 (C=%d W=%d)", C, W);
+  if (dtype == ASR_BF16 && !mfma_supported(C, W) && !convb_supported(W, C))
+    return fail(ASR_E_UNSUPPORTED, "bf16 conv needs C in {16,32,64} and W in {32, 16, 8} (C=%d W=%d)", C, W);
   const StackWs Lw = stack_ws_layout(N, H, W, C, L, dtype);
+  if (Lw.img) ASR_TRY(stack_img_check_strides("asr_block_stack_backward", dtype, 0, 0, w_stride, 0, x_stride));
   if (!ws || ws_bytes < Lw.total) return fail(ASR_E_WORKSPACE, "asr_block_stack_backward: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   unsigned char* base = (unsigned char*)ws;
   const size_t es = dtype == ASR_BF16 ? 2 : 4, act = (size_t)N * H * W * C * es;
   const long E = 9L * C * C;
+  if (Lw.img) {  // input gradients in one launch (a workgroup per image), then every layer's weight gradient in one
+    const long P = (long)N * H * W * C, sst = (long)Lw.rows * (E + C), gst = (long)reduce_groups(Lw.rows) * (E + C);
+    float* slabs = (float*)(base + Lw.slabs);
+    float* grp = (float*)(base + Lw.grp);
+    int nsl = 0;
+    if (dtype == ASR_BF16) {
+      ASR_TRY(stage_img_backward(dyL, base + Lw.dys, P, dx0, masks, mask_stride, w, w_stride, h, 2.f * gamma, N, H, W,
+                                 C, L, s));
+      if (dparams)
+        ASR_TRY(wgradb_layers(xs, x_stride, base + Lw.dys, P, masks, mask_stride, h, N, H, W, C, L, slabs, sst, &nsl, s));
+    } else {
+      ASR_TRY(stage_img32_backward((const float*)dyL, (float*)(base + Lw.dys), P, (float*)dx0, masks, mask_stride,
+                                   (const float*)w, w_stride, h, 2.f * gamma, N, H, W, C, L, s));
+      if (dparams)
+        ASR_TRY(wgrad32_layers((const float*)xs, x_stride, (const float*)(base + Lw.dys), P, masks, mask_stride, h, N,
+                               H, W, C, L, slabs, sst, &nsl, s));
+    }
+    if (!dparams) return ASR_OK;
+    if (nsl > Lw.rows)
+      return fail(ASR_E_WORKSPACE, "asr_block_stack_backward: %d slab rows > the workspace's %d", nsl, Lw.rows);
+    ASR_TRY(reduce_slab_layers(slabs, sst, nsl, E + C, grp, gst, L, s));
+    return project_layers(grp, gst, reduce_groups(nsl), E, C, theta_dst, n_theta, L, dparams, n_theta + C, s);
+  }
   if (Lw.deep) {
     if (w_stride != (long)asr_wpack_elems(C))
       return fail(ASR_E_ARG, "asr_block_stack_backward: w_stride must be asr_wpack_elems(C) on the fused path");

@@ -168,8 +168,14 @@ long asr_mask_bytes(int N, int H, int W, int C);
  * elements; bias: layer l's at bias + l*bias_stride (may be NULL).  bf16 at
  * C=16, H=W=32 runs all L steps in one launch with every image resident in
  * LDS; bf16 at C=64, W=32 (store_all) runs all L steps in one launch with
- * whole images per workgroup; other shapes run the per-block kernels in
- * sequence. */
+ * whole images per workgroup; the image-resident stage shapes (bf16 at
+ * 16x16x32, 8x8x64 and 8x8x32, fp32 at 16x16x32 and 8x8x64; H == W) run all L
+ * steps in one launch with a workgroup per image, when store_all != 0 and
+ * bias and masks are both given (without one of them the per-block sequence
+ * runs).  On that path the strides must keep every layer's vector accesses
+ * aligned, else ASR_E_ARG before any launch: y_stride % 4, mask_stride % 2,
+ * bias_stride % 4 and, in bf16, w_stride % 8.  Other shapes (bf16: C in
+ * {16,32,64}, W in {32,16,8}) run the per-block kernels in sequence. */
 int asr_block_stack_forward(const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride,
                             const void* w, long w_stride, const float* bias, long bias_stride, float h,
                             int N, int H, int W, int C, int L, int dtype, int store_all, asr_stream_t stream);
@@ -182,7 +188,12 @@ int asr_block_stack_forward(const void* x0, void* ys, long y_stride, uint8_t* ma
  * H=W=32 runs one fused launch with dx resident in LDS (w_stride must be
  * asr_wpack_elems(16)); bf16 at C=64, W=32 runs one launch over all blocks
  * (whole images per workgroup, weight-gradient slabs reduced in-launch);
- * other shapes run asr_conv_backward per block. */
+ * the image-resident stage shapes of asr_block_stack_forward run one launch
+ * for the input gradients (a workgroup per image) and, with dparams, one for
+ * every layer's weight gradient (x_stride % 8 and w_stride % 8 in bf16,
+ * x_stride % 4 in fp32, else ASR_E_ARG before any launch); other shapes run
+ * asr_conv_backward per block.  The operator is the antisymmetric one: the
+ * forward's w with A^T = -A + 2*gamma*I. */
 size_t asr_block_stack_backward_workspace_bytes(int N, int H, int W, int C, int L, int dtype);
 int asr_block_stack_backward(const void* dyL, const void* xs, long x_stride, const uint8_t* masks, long mask_stride,
                              const void* w, long w_stride, const int32_t* theta_dst, long n_theta, float h,

@@ -193,6 +193,60 @@ def test_fused_c16_forward_checks_weight_stride(lib):
     assert rc == _lib.ASR_E_ARG
 
 
+STAGE_IMG_SHAPES = [(1, 16, 32), (1, 8, 64), (1, 8, 32), (0, 16, 32), (0, 8, 64)]  # (dtype, H = W, C), asr_api.hip
+
+
+@pytest.mark.parametrize("dt,HW,C", STAGE_IMG_SHAPES)
+def test_stage_img_stack_checks_strides(lib, dt, HW, C):
+    """At an image-resident stage shape the stack ABI refuses, before any launch, every per-layer
+    stride its kernels' vector accesses cannot take: y_stride % 4 (8-B / 16-B y stores),
+    mask_stride % 2 (2-B mask stores), bias_stride % 4 (16-B loads), x_stride % 8 (bf16) or % 4
+    (fp32) in the backward's weight gradient and, in bf16, w_stride % 8 (16-B fragment loads; the
+    fp32 kernels read W with scalar loads)."""
+    from differential_equations_resnet_amd import _lib
+    N, L = 3, 2
+    fake = ct.c_void_p(256)  # never dereferenced: the checks come first
+    P, mb = N * HW * HW * C, lib.asr_mask_bytes(N, HW, HW, C)
+    wst = lib.asr_wpack_elems(C) if dt == _lib.ASR_BF16 else 9 * C * C
+    assert P % 8 == 0 and mb % 2 == 0 and wst % 8 == 0
+
+    def fwd(y=P, m=mb, w=wst, b=C):
+        return lib.asr_block_stack_forward(fake, fake, y, fake, m, fake, w, fake, b, ct.c_float(0.1), N, HW, HW, C, L,
+                                           dt, 1, None)
+
+    bad = [("y_stride", dict(y=P + 2)), ("mask_stride", dict(m=mb + 1)), ("bias_stride", dict(b=C + 2))]
+    if dt == _lib.ASR_BF16:
+        bad.append(("w_stride", dict(w=wst + 4)))
+    for name, kw in bad:
+        assert fwd(**kw) == _lib.ASR_E_ARG, kw
+        assert name in lib.asr_last_error().decode()
+    need = lib.asr_block_stack_backward_workspace_bytes(N, HW, HW, C, L, dt)
+
+    def bwd(x=P, w=wst, ws_bytes=need):
+        return lib.asr_block_stack_backward(fake, fake, x, fake, mb, fake, w, fake, 8, ct.c_float(0.1),
+                                            ct.c_float(0.0), N, HW, HW, C, L, dt, fake, fake, fake, ws_bytes, None)
+
+    assert bwd(x=P + (4 if dt == _lib.ASR_BF16 else 2)) == _lib.ASR_E_ARG
+    if dt == _lib.ASR_BF16:
+        assert bwd(w=wst + 4) == _lib.ASR_E_ARG
+    assert bwd(ws_bytes=need - 1) == _lib.ASR_E_WORKSPACE
+
+
+@pytest.mark.parametrize("dt,HW,C", STAGE_IMG_SHAPES)
+def test_stage_img_stack_workspace_size(lib, dt, HW, C):
+    """asr_block_stack_backward_workspace_bytes at an image-resident stage shape holds the
+    gradient entering every layer (L activations) and L layers' weight-gradient slabs of at
+    least one [dW | db] row each; it grows with L by at least that much."""
+    from differential_equations_resnet_amd import _lib
+    N = 5
+    act = N * HW * HW * C * (2 if dt == _lib.ASR_BF16 else 4)
+    row = (9 * C * C + C) * 4
+    sizes = [lib.asr_block_stack_backward_workspace_bytes(N, HW, HW, C, L, dt) for L in (1, 2, 3)]
+    for L, b in zip((1, 2, 3), sizes):
+        assert b >= L * (act + row), (L, b)
+    assert sizes[1] - sizes[0] >= act + row and sizes[2] - sizes[1] >= act + row
+
+
 def test_forward_backward_rejects_inference_workspace_before_launching(lib):
     """asr_net_forward_backward on an ASR_VARIANT_INFERENCE workspace fails with
     ASR_E_ARG before any launch, for every parameter kind (the regular kind's

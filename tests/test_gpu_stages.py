@@ -301,6 +301,29 @@ def test_stages_network_bf16_odd_batch():
     _assert_bf16_net(ex, spec, params, imgs, onehot)
 
 
+STAGES_8x8x32 = [(16, 1, 0), (32, 2, 2)]  # on a 16 x 16 input: 16^2 x 16, then 8^2 x 32
+
+
+def test_stages_network_bf16_8x8x32():
+    """The 8 x 8 x 32 image-resident stage (k_stagef<32, 8> / k_stageb<32, 8>), which no 32 x 32 input
+    of the He layout reaches: a 16 x 16 input, an odd batch."""
+    from differential_equations_resnet_amd.runtime import StagesExecutor
+    spec, params, imgs, onehot = _stages_setup(STAGES_8x8x32, "3by3", True, h=0.25, H=16, W=16, N=5)
+    ex = StagesExecutor(imgs.shape[0], spec.H, spec.W, 3, STAGES_8x8x32, 10, spec.h, spec.gamma, subtract_mean=127.5,
+                        divide_by_stddev=127.5, input_u8=True, param_kind=KINDS["3by3"], antisymmetric=True,
+                        dtype="bfloat16")
+    _assert_bf16_net(ex, spec, params, imgs, onehot)
+
+
+def test_stages_network_fp32_8x8x32():
+    """The same stages in fp32 (8 x 8 x 32 is not an fp32 image-resident shape: the per-block kernels)."""
+    from differential_equations_resnet_amd.runtime import StagesExecutor
+    spec, params, imgs, onehot = _stages_setup(STAGES_8x8x32, "3by3", True, H=16, W=16, N=5)
+    ex = StagesExecutor(imgs.shape[0], spec.H, spec.W, 3, STAGES_8x8x32, 10, spec.h, spec.gamma, subtract_mean=127.5,
+                        divide_by_stddev=127.5, input_u8=True, param_kind=KINDS["3by3"], antisymmetric=True)
+    _check_net(ex, spec, params, imgs, onehot)
+
+
 def test_stages_bf16_unsupported_width_raises():
     from differential_equations_resnet_amd import _lib
     from differential_equations_resnet_amd.runtime import StagesExecutor
