@@ -22,6 +22,19 @@ static int check_shape(int N, int H, int W, int C) {
   return ASR_OK;
 }
 
+// the shapes of the bf16 3 x 3 kernels (MFMA at W = 32, the any-width convb_* at W = 16 / 8)
+static int check_bf16_conv(int C, int W) {
+  if (!mfma_supported(C, W) && !convb_supported(W, C))
+    return fail(ASR_E_UNSUPPORTED, "bf16 conv needs C in {16,32,64} and W in {32, 16, 8} (C=%d W=%d)", C, W);
+  return ASR_OK;
+}
+
+static int check_kernel_size(const char* fn, int kernel_size) {
+  if (kernel_size < 1 || kernel_size > 15 || !(kernel_size & 1))
+    return fail(ASR_E_ARG, "%s: kernel_size %d (odd, 1..15)", fn, kernel_size);
+  return ASR_OK;
+}
+
 // ---------------------------------------------------------------------------
 // conv backward workspace
 // ---------------------------------------------------------------------------
@@ -37,17 +50,30 @@ static BwdWs bwd_ws_layout(int N, int H, int W, int C, int dtype, int stages = 1
   const long E = (long)K * K * C * C;
   const long P = (long)N * H * W * C;
   const int nsl = slab_rows >= 0 ? slab_rows : kMaxBlockSlabs * stages;
-  size_t off = 0;
-  b.dz = off;
-  if (dtype == ASR_F32) off += align_up((size_t)P * 4, 256);
-  b.slabs = off;
-  off += align_up((size_t)nsl * (E + C) * 4, 256);
-  b.red = off;
-  off += align_up(reduce_ws_bytes(nsl, E + C), 256);
-  b.g = off;
-  if (stages > 1) off += align_up((size_t)P * (dtype == ASR_BF16 ? 2 : 4), 256);
-  b.total = off;
+  WsCursor c;
+  b.dz = c.take(dtype == ASR_F32 ? (size_t)P * 4 : 0);
+  b.slabs = c.take((size_t)nsl * (E + C) * 4);
+  b.red = c.take(reduce_ws_bytes(nsl, E + C));
+  b.g = c.take(stages > 1 ? (size_t)P * (dtype == ASR_BF16 ? 2 : 4) : 0);
+  b.total = c.off;
   return b;
+}
+
+// The stem's backward workspace (the network executor's bwdws area, shared with
+// the blocks' BwdWs): dz1 in fp32, conv1's weight-gradient slabs, reduce_and_project's rows.
+struct StemWs {
+  size_t dz, slabs, red, total;
+};
+
+static StemWs stem_ws_layout(long P, int Cin, int C) {
+  StemWs w{};
+  const long ES1 = 9L * Cin * C + C;
+  WsCursor c;
+  w.dz = c.take((size_t)P * 4);
+  w.slabs = c.take((size_t)kMaxBlockSlabs * ES1 * 4);
+  w.red = c.take(reduce_ws_bytes(kMaxBlockSlabs, ES1));
+  w.total = c.off;
+  return w;
 }
 
 // One conv application's backward: dx = [dy] + extra + A^T dz and the
@@ -85,29 +111,6 @@ static int block_backward(int mode, const void* dy, const void* x, const uint8_t
     ASR_TRY(conv_f32((euler && !skip_dy) ? B_EULER : B_CONV, dz_scratch, dx, nullptr, (const float*)w, nullptr, h,
                      2.f * gamma, (const float*)dy, N, H, W, C, C, 0, s, (const float*)extra));
   if (need_w) ASR_TRY(wgrad_f32(x, 0, dz_scratch, N, H, W, C, C, slabs, nsl, s));
-  return ASR_OK;
-}
-
-static int conv_backward_impl(int mode, const void* dy, const void* x, const uint8_t* mask, const void* w,
-                              const int32_t* theta_dst, long n_theta, float h, float gamma, int N, int H, int W,
-                              int C, int dtype, void* dx, float* dtheta, float* dbias, float* dw_hwio, void* ws,
-                              hipStream_t s, float* grp_defer = nullptr, int* nsl_out = nullptr, bool relu_dx = false,
-                              int* relu_done = nullptr) {
-  const BwdWs L = bwd_ws_layout(N, H, W, C, dtype);
-  unsigned char* base = (unsigned char*)ws;
-  float* slabs = (float*)(base + L.slabs);
-  float* red = (float*)(base + L.red);
-  const bool need_w = dtheta || dbias || dw_hwio;
-  int nsl = 0;
-  ASR_TRY(block_backward(mode, dy, x, mask, w, h, gamma, N, H, W, C, dtype, dx, need_w || grp_defer, nullptr, false,
-                         slabs, (float*)(base + L.dz), &nsl, s, relu_dx, relu_done));
-  if (grp_defer) {  // the network defers pass 2 + projection to one launch for all layers
-    if (nsl_out) *nsl_out = nsl;
-    return reduce_slabs_to_groups(slabs, nsl, 9L * C * C + C, grp_defer, s);
-  }
-  if (need_w)
-    ASR_TRY(reduce_and_project(slabs, nsl, 9L * C * C, C, dtheta ? theta_dst : nullptr, n_theta, dtheta, dbias,
-                               dw_hwio, red, s));
   return ASR_OK;
 }
 
@@ -290,6 +293,8 @@ struct NetLayout {
   size_t theta_dst_pr;  // the pull-back from the pair-local slabs (stack_pair)
   int f32_rows;         // fp32: slab rows of one block application's weight gradient (f32_block_slab_rows)
   size_t grow;        // stacked Euler backward: dL/dx_L as one bf16 row per image (the GAP gradient) [N][C]
+  BwdWs bw;           // inside bwdws: one block's backward workspace (asr_conv_backward's layout) ...
+  StemWs stem;        // ... and, after the blocks, the stem's
 };
 
 static int net_check(const asr_net_config* c) {
@@ -340,54 +345,47 @@ static NetLayout net_layout(const asr_net_config* c) {
   L.stack_bwd = tr && c->dtype == ASR_BF16 && block_stack_bwd_supported(c->N, c->H, c->W, C);
   L.stack_grid = L.stack_bwd ? block_stack_bwd_grid(c->N) : 0;
   L.stack_pair = L.stack_bwd && !L.sep_bwd;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += align_up(bytes, 256);
-    return o;
-  };
-  L.w_src = take((size_t)L.E * 4);
-  L.w_src_bwd = take(L.sep_bwd && tr ? (size_t)L.E * 4 : 0);
-  L.theta_dst = take((size_t)L.ntheta * 2 * 4);
-  L.wbuf = take((size_t)c->L * L.wstride * L.act_bytes);
-  L.wbuf_bwd = take(L.sep_bwd && tr ? (size_t)c->L * L.wstride * L.act_bytes : 0);
-  L.x0 = take(L.fast_stem ? 0 : (size_t)c->N * c->H * c->W * c->Cin * 4);
+  WsCursor ws;
+  L.w_src = ws.take((size_t)L.E * 4);
+  L.w_src_bwd = ws.take(L.sep_bwd && tr ? (size_t)L.E * 4 : 0);
+  L.theta_dst = ws.take((size_t)L.ntheta * 2 * 4);
+  L.wbuf = ws.take((size_t)c->L * L.wstride * L.act_bytes);
+  L.wbuf_bwd = ws.take(L.sep_bwd && tr ? (size_t)c->L * L.wstride * L.act_bytes : 0);
+  L.x0 = ws.take(L.fast_stem ? 0 : (size_t)c->N * c->H * c->W * c->Cin * 4);
   // training keeps x_0 .. x_L for the backward; inference ping-pongs (x_0 + 2 slots)
-  L.acts = take((size_t)(tr ? c->L + 1 : 3) * L.P * L.act_bytes);
-  L.xmids = take(L.rk2 ? (size_t)(tr ? c->L : 1) * L.P * L.act_bytes : 0);
-  L.masks = take(tr ? (size_t)L.stages * c->L * L.mask_bytes : 0);  // RK2: mask1 of every block, then mask2
-  L.dxa = take(tr ? (size_t)L.P * L.act_bytes : 0);
-  L.dxb = take(tr ? (size_t)L.P * L.act_bytes : 0);
-  L.dxg = take(L.rk2 && tr ? (size_t)L.P * L.act_bytes : 0);
+  L.acts = ws.take((size_t)(tr ? c->L + 1 : 3) * L.P * L.act_bytes);
+  L.xmids = ws.take(L.rk2 ? (size_t)(tr ? c->L : 1) * L.P * L.act_bytes : 0);
+  L.masks = ws.take(tr ? (size_t)L.stages * c->L * L.mask_bytes : 0);  // RK2: mask1 of every block, then mask2
+  L.dxa = ws.take(tr ? (size_t)L.P * L.act_bytes : 0);
+  L.dxb = ws.take(tr ? (size_t)L.P * L.act_bytes : 0);
+  L.dxg = ws.take(L.rk2 && tr ? (size_t)L.P * L.act_bytes : 0);
   // per-block backward workspace (asr_conv_backward layout), reused by the stem.
   // fp32 keeps every block's slabs in slabs_all, sized by the grid its weight
   // gradient runs (not the 512-row maximum): no slab rows here, no slabs2
   const bool f32 = c->dtype == ASR_F32;
   L.f32_rows = f32 ? f32_block_slab_rows(c->N, c->H, c->W, C) : 0;
-  const BwdWs bw = bwd_ws_layout(c->N, c->H, c->W, C, c->dtype, L.stages, 3, f32 ? 0 : -1);
-  const long E1 = 9L * c->Cin * C;
-  const size_t stem_ws = align_up((size_t)L.P * 4, 256) + align_up((size_t)kMaxBlockSlabs * (E1 + C) * 4, 256) +
-                         align_up(reduce_ws_bytes(kMaxBlockSlabs, E1 + C), 256);
-  L.bwdws = take(tr ? std::max(bw.total, stem_ws) : 0);
+  L.bw = bwd_ws_layout(c->N, c->H, c->W, C, c->dtype, L.stages, 3, f32 ? 0 : -1);
+  L.stem = stem_ws_layout(L.P, c->Cin, C);
+  L.bwdws = ws.take(tr ? std::max(L.bw.total, L.stem.total) : 0);
   // odd Euler blocks' slabs (even ones use the backward workspace's): a
   // block's slabs stay readable while the next block's kernel reduces them
-  L.slabs2 = take(tr && !f32 ? (size_t)L.stages * kMaxBlockSlabs * (L.E + C) * 4 : 0);  // every other block's slabs
+  L.slabs2 = ws.take(tr && !f32 ? (size_t)L.stages * kMaxBlockSlabs * (L.E + C) * 4 : 0);  // every other block's slabs
   const int rows = f32 ? L.stages * L.f32_rows : L.stages * kMaxBlockSlabs;
   L.grp_stride = (long)reduce_groups(rows) * (L.E + C);
-  L.grp = take(tr ? (size_t)c->L * L.grp_stride * 4 : 0);
+  L.grp = ws.take(tr ? (size_t)c->L * L.grp_stride * 4 : 0);
   L.slab_stride = (long)rows * (L.E + C);
-  L.slabs_all = take(tr && f32 ? (size_t)c->L * L.slab_stride * 4 : 0);
-  L.deep_slabs = take(L.deep && tr ? deep16_slab_bytes(c->N, c->L) : 0);
-  L.theta_dst_tm = take(L.stack_bwd ? (size_t)L.ntheta * 2 * 4 : 0);
-  L.theta_dst_pr = take(L.stack_pair ? (size_t)L.ntheta * 2 * 4 : 0);
-  L.stack_slabs = take(L.stack_bwd ? (size_t)c->L * L.stack_grid * (L.E + C) * 4 : 0);
-  L.stack_done = take(L.stack_bwd ? (size_t)stack_done_words(c->L) * 4 : 0);
-  L.grow = take(L.stack_bwd && !L.rk2 ? (size_t)c->N * C * 2 : 0);
-  L.probs = take((size_t)c->N * K * 4);
-  L.loss_per = take(tr ? (size_t)c->N * 4 : 0);
-  L.dlogits = take(tr ? (size_t)c->N * K * 4 : 0);
-  L.gap = take(tr ? (size_t)c->N * C * 4 : 0);
-  L.total = off;
+  L.slabs_all = ws.take(tr && f32 ? (size_t)c->L * L.slab_stride * 4 : 0);
+  L.deep_slabs = ws.take(L.deep && tr ? deep16_slab_bytes(c->N, c->L) : 0);
+  L.theta_dst_tm = ws.take(L.stack_bwd ? (size_t)L.ntheta * 2 * 4 : 0);
+  L.theta_dst_pr = ws.take(L.stack_pair ? (size_t)L.ntheta * 2 * 4 : 0);
+  L.stack_slabs = ws.take(L.stack_bwd ? (size_t)c->L * L.stack_grid * (L.E + C) * 4 : 0);
+  L.stack_done = ws.take(L.stack_bwd ? (size_t)stack_done_words(c->L) * 4 : 0);
+  L.grow = ws.take(L.stack_bwd && !L.rk2 ? (size_t)c->N * C * 2 : 0);
+  L.probs = ws.take((size_t)c->N * K * 4);
+  L.loss_per = ws.take(tr ? (size_t)c->N * 4 : 0);
+  L.dlogits = ws.take(tr ? (size_t)c->N * K * 4 : 0);
+  L.gap = ws.take(tr ? (size_t)c->N * C * 4 : 0);
+  L.total = ws.off;
   return L;
 }
 
@@ -539,6 +537,64 @@ static int net_forward_impl(const asr_net_config* c, const NetLayout& L, const f
   return timed_event(c, 1, s);
 }
 
+// ---------------------------------------------------------------------------
+// A stage whose L Euler blocks run fused: the host sequence behind the stack
+// ABI (asr_block_stack_*, below) and the multi-stage executor (asr_stages.hip)
+// ---------------------------------------------------------------------------
+int fused_stage_kind(int H, int W, int C, int dtype) {
+  if (dtype == ASR_BF16 && deep16_supported(H, W, C)) return kFusedDeep16;
+  return stage_img_supported(H, W, C, dtype) ? kFusedImg : kFusedNone;
+}
+
+// x0 -> ys (layer l's output at ys + l y_stride, its relu mask at masks + l mask_stride), one launch.  deep16 also
+// takes store_all = false (x_L only, at ys) and null masks; the image-resident kernels need every output, bias and
+// masks.
+int fused_stage_forward(int kind, int dtype, const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride,
+                        const void* w, long w_stride, const float* bias, long bias_stride, float h, int N, int H, int W,
+                        int C, int L, bool store_all, hipStream_t s) {
+  if (kind == kFusedDeep16)
+    return deep16_forward(x0, ys, y_stride, masks, mask_stride, w, bias, bias_stride, h, N, L, store_all, s);
+  if (kind != kFusedImg || !store_all)
+    return fail(ASR_E_ARG, "fused_stage_forward: kind %d, store_all %d", kind, store_all);
+  return stage_img_forward(dtype, x0, ys, y_stride, masks, mask_stride, w, w_stride, bias, bias_stride, h, N, H, W, C,
+                           L, s);
+}
+
+// Its backward.  d holds dL/dx_L; dx_0 ends in d or in e (*in_e).  deep16 ping-pongs between the two (d is
+// overwritten; dx0_copy, nullable: dx_0 is also copied there, right behind the kernel); the image-resident kernel
+// reads d, writes e and stores the gradient entering each layer at dys ([L][N H W C], unpadded).
+// dparams == nullptr: input gradient only.  Else every layer's weight gradient: slabs [L][slab_stride] (the
+// caller's room: slab_rows rows a layer; ASR_E_WORKSPACE if the launch wrote another count), pass 1 into
+// grp [L][grp_stride], pass 2 + projection onto theta: [dtheta | dbias] of layer l at dparams + l dp_stride.
+int fused_stage_backward(const char* who, int kind, int dtype, void* d, void* e, int* in_e, void* dx0_copy, void* dys,
+                         const void* xs, long x_stride, const uint8_t* masks, long mask_stride, const void* w,
+                         long w_stride, float h, float two_gamma, int N, int H, int W, int C, int L, float* slabs,
+                         long slab_stride, int slab_rows, float* grp, long grp_stride, const int32_t* theta_dst,
+                         long n_theta, float* dparams, long dp_stride, hipStream_t s) {
+  const long E = 9L * C * C, P = (long)N * H * W * C;
+  int rows = 0;
+  if (kind == kFusedDeep16) {  // dx resident in LDS, one slab set per layer
+    ASR_TRY(deep16_backward(d, e, xs, x_stride, masks, mask_stride, w, h, two_gamma, N, L, slabs, &rows, in_e, s));
+    if (dx0_copy)
+      ASR_TRY(hip_check(hipMemcpyAsync(dx0_copy, *in_e ? e : d, (size_t)P * 2, hipMemcpyDeviceToDevice, s),
+                        "hipMemcpyAsync"));
+    if (!dparams) return ASR_OK;
+    if (rows != slab_rows) return fail(ASR_E_WORKSPACE, "%s: deep16 slab rows %d != %d", who, rows, slab_rows);
+    ASR_TRY(reduce_slabs_to_groups(slabs, L * rows, E + C, grp, s));
+    return project_layers(grp, grp_stride, reduce_groups(rows), E, C, theta_dst, n_theta, L, dparams, dp_stride, s);
+  }
+  if (kind != kFusedImg) return fail(ASR_E_ARG, "%s: not a fused stage", who);
+  // input gradients in one launch (a workgroup per image), then every layer's weight gradient in one: x_l and
+  // the gradient entering layer l, dys + l P
+  *in_e = 1;
+  ASR_TRY(stage_img_backward(dtype, d, dys, P, e, masks, mask_stride, w, w_stride, h, two_gamma, N, H, W, C, L, s));
+  if (!dparams) return ASR_OK;
+  ASR_TRY(wgrad_layers(dtype, xs, x_stride, dys, P, masks, mask_stride, h, N, H, W, C, L, slabs, slab_stride, &rows, s));
+  if (rows > slab_rows) return fail(ASR_E_WORKSPACE, "%s: %d slab rows > the workspace's %d", who, rows, slab_rows);
+  ASR_TRY(reduce_slab_layers(slabs, slab_stride, rows, E + C, grp, grp_stride, L, s));
+  return project_layers(grp, grp_stride, reduce_groups(rows), E, C, theta_dst, n_theta, L, dparams, dp_stride, s);
+}
+
 }  // namespace asr
 
 using namespace asr;
@@ -557,11 +613,9 @@ int asr_conv_forward(int mode, const void* x, void* y, uint8_t* mask, const void
   if (mode != ASR_MODE_EULER && mode != ASR_MODE_CONV) return fail(ASR_E_ARG, "asr_conv_forward: bad mode %d", mode);
   hipStream_t s = (hipStream_t)stream;
   if (dtype == ASR_BF16) {
-    if (!mfma_supported(C, W)) {  // W = 16 / 8 (multi-stage nets): the any-width bf16 kernels, Euler block or bare conv
-      if (convb_supported(W, C))
-        return convb_forward(x, y, mask, w, bias, h, N, H, W, C, s, mode == ASR_MODE_CONV);
-      return fail(ASR_E_UNSUPPORTED, "bf16 conv needs C in {16,32,64} and W in {32, 16, 8} (C=%d W=%d)", C, W);
-    }
+    ASR_TRY(check_bf16_conv(C, W));
+    if (!mfma_supported(C, W))  // W = 16 / 8 (multi-stage nets): the any-width bf16 kernels, Euler block or bare conv
+      return convb_forward(x, y, mask, w, bias, h, N, H, W, C, s, mode == ASR_MODE_CONV);
     if (mode == ASR_MODE_EULER && deep16_supported(H, W, C))
       return deep16_forward(x, y, 0, mask, 0, w, bias, 0, h, N, 1, true, s);
     return block_fwd_mfma(mode == ASR_MODE_EULER ? 0 : 1, x, nullptr, y, mask, w, bias, h, N, H, W, C, s);
@@ -572,12 +626,7 @@ int asr_conv_forward(int mode, const void* x, void* y, uint8_t* mask, const void
   return fail(ASR_E_ARG, "asr_conv_forward: bad dtype %d", dtype);
 }
 
-// the image-resident stage kernels (k_stagef / k_stageb, k_stagef32 / k_stageb32) behind the stack ABI
-static bool stack_img_supported(int H, int W, int C, int dtype) {
-  return dtype == ASR_BF16 ? stage_img_supported(H, W, C) : dtype == ASR_F32 && stage_img32_supported(H, W, C);
-}
-
-// Their vector accesses need per-layer strides that keep every layer aligned
+// The image-resident stage kernels' vector accesses need per-layer strides that keep every layer aligned
 // (a stride of 0 means "not passed to this call").  bf16: 8-B y stores, 2-B
 // mask stores, 16-B W fragment / bias / x (k_wgradb) loads; fp32: 16-B y
 // stores and bias / x (k_wgrad32) loads, 2-B mask stores, scalar W loads.
@@ -601,25 +650,23 @@ int asr_block_stack_forward(const void* x0, void* ys, long y_stride, uint8_t* ma
   if (store_all && L > 1 && y_stride < (long)N * H * W * C)
     return fail(ASR_E_ARG, "asr_block_stack_forward: y_stride smaller than one activation");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == ASR_BF16 && deep16_supported(H, W, C)) {
+  const int fused = fused_stage_kind(H, W, C, dtype);
+  if (fused == kFusedDeep16) {
     if (L > 1 && w_stride != (long)asr_wpack_elems(C))
       return fail(ASR_E_ARG, "asr_block_stack_forward: w_stride must be asr_wpack_elems(C) on the fused path");
-    return deep16_forward(x0, ys, y_stride, masks, mask_stride, w, bias, bias_stride, h, N, L, store_all != 0, s);
+    return fused_stage_forward(fused, dtype, x0, ys, y_stride, masks, mask_stride, w, w_stride, bias, bias_stride, h, N,
+                               H, W, C, L, store_all != 0, s);
   }
-  if (dtype == ASR_BF16 && !mfma_supported(C, W) && !convb_supported(W, C))
-    return fail(ASR_E_UNSUPPORTED, "bf16 conv needs C in {16,32,64} and W in {32, 16, 8} (C=%d W=%d)", C, W);
+  if (dtype == ASR_BF16) ASR_TRY(check_bf16_conv(C, W));
   if (dtype != ASR_F32 && dtype != ASR_BF16) return fail(ASR_E_ARG, "asr_block_stack_forward: bad dtype");
   const size_t es = dtype == ASR_BF16 ? 2 : 4;
   if (!store_all && L > 1) return fail(ASR_E_UNSUPPORTED, "asr_block_stack_forward: store_all=0 needs the fused path");
   // image-resident stages: all L blocks in one launch, a workgroup per image.  The kernels store every
   // layer and read bias and masks unconditionally; calls without them take the per-block sequence.
-  if (stack_img_supported(H, W, C, dtype) && store_all && bias && masks) {
+  if (fused == kFusedImg && store_all && bias && masks) {
     ASR_TRY(stack_img_check_strides("asr_block_stack_forward", dtype, y_stride, mask_stride, w_stride, bias_stride, 0));
-    if (dtype == ASR_BF16)
-      return stage_img_forward(x0, ys, y_stride, masks, mask_stride, w, w_stride, bias, bias_stride, h, N, H, W, C, L,
-                               s);
-    return stage_img32_forward((const float*)x0, (float*)ys, y_stride, masks, mask_stride, (const float*)w, w_stride,
-                               bias, bias_stride, h, N, H, W, C, L, s);
+    return fused_stage_forward(fused, dtype, x0, ys, y_stride, masks, mask_stride, w, w_stride, bias, bias_stride, h, N,
+                               H, W, C, L, true, s);
   }
   if (dtype == ASR_BF16 && block_stack_fwd_supported(N, H, W, C))
     return block_stack_fwd_mfma(x0, ys, L > 1 ? y_stride : (long)N * H * W * C, masks, mask_stride, w, w_stride, bias,
@@ -638,55 +685,69 @@ int asr_block_stack_forward(const void* x0, void* ys, long y_stride, uint8_t* ma
 // fused path's slabs + group rows or one per-block backward workspace
 struct StackWs {
   size_t da, db, slabs, grp, blk, done, tdst, g, dys, total;
-  bool deep, stack64, img;
+  int fused;  // fused_stage_kind (RK2: kFusedNone)
+  bool stack64;
   int grid;
-  int rows;  // img: slab rows per layer (f32_block_slab_rows)
+  int rows;  // fused: the slab rows per layer the workspace holds
 };
 static StackWs stack_ws_layout(int N, int H, int W, int C, int L, int dtype, bool rk2 = false) {
   StackWs w{};
-  const size_t act = align_up((size_t)N * H * W * C * (dtype == ASR_BF16 ? 2 : 4), 256);
+  const size_t act = (size_t)N * H * W * C * (dtype == ASR_BF16 ? 2 : 4);
   const long ES = 9L * C * C + C;
-  w.deep = !rk2 && dtype == ASR_BF16 && deep16_supported(H, W, C);
-  w.stack64 = dtype == ASR_BF16 && !w.deep && block_stack_bwd_supported(N, H, W, C);
+  w.fused = rk2 ? kFusedNone : fused_stage_kind(H, W, C, dtype);
+  w.stack64 = dtype == ASR_BF16 && w.fused == kFusedNone && block_stack_bwd_supported(N, H, W, C);
   w.grid = w.stack64 ? block_stack_bwd_grid(N) : 0;
-  w.img = !rk2 && !w.deep && !w.stack64 && stack_img_supported(H, W, C, dtype);
-  size_t off = 0;
-  w.da = off;
-  off += act;
-  w.db = off;
-  off += act;
-  if (w.img) {  // the gradient entering every layer (L activations, unpadded), slabs [L][rows][ES], group rows
+  WsCursor c;
+  w.da = c.take(act);
+  w.db = c.take(act);
+  if (w.fused == kFusedImg) {  // the gradient entering every layer (L activations, unpadded), slabs [L][rows][ES], grp
     w.rows = f32_block_slab_rows(N, H, W, C);
-    w.dys = off;
-    off += align_up((size_t)L * N * H * W * C * (dtype == ASR_BF16 ? 2 : 4), 256);
-    w.slabs = off;
-    off += align_up((size_t)L * w.rows * ES * 4, 256);
-    w.grp = off;
-    off += align_up((size_t)L * reduce_groups(w.rows) * ES * 4, 256);
-  } else if (w.deep) {
-    w.slabs = off;
-    off += align_up(deep16_slab_bytes(N, L), 256);
-    w.grp = off;
-    off += align_up((size_t)L * reduce_groups(kMaxBlockSlabs) * ES * 4, 256);
+    w.dys = c.take(L * act);
+    w.slabs = c.take((size_t)L * w.rows * ES * 4);
+    w.grp = c.take((size_t)L * reduce_groups(w.rows) * ES * 4);
+  } else if (w.fused == kFusedDeep16) {
+    w.rows = (int)(deep16_slab_bytes(N, 1) / ((size_t)ES * 4));
+    w.slabs = c.take(deep16_slab_bytes(N, L));
+    w.grp = c.take((size_t)L * reduce_groups(kMaxBlockSlabs) * ES * 4);
   } else if (w.stack64) {  // slabs [L][grid][ES] (tile-major dW), group rows, counters, tile-major theta map
-    w.slabs = off;
-    off += align_up((size_t)L * w.grid * ES * 4, 256);
-    w.grp = off;
-    off += align_up((size_t)L * reduce_groups(w.grid) * ES * 4, 256);
-    w.done = off;
-    off += align_up((size_t)stack_done_words(L) * 4, 256);
-    w.tdst = off;
-    off += align_up((size_t)2 * 9 * C * C * 4, 256);
-    if (rk2) {  // the gradient reaching x_mid between a block's two stages
-      w.g = off;
-      off += act;
-    }
+    w.slabs = c.take((size_t)L * w.grid * ES * 4);
+    w.grp = c.take((size_t)L * reduce_groups(w.grid) * ES * 4);
+    w.done = c.take((size_t)stack_done_words(L) * 4);
+    w.tdst = c.take((size_t)2 * 9 * C * C * 4);
+    if (rk2) w.g = c.take(act);  // the gradient reaching x_mid between a block's two stages
   } else {
-    w.blk = off;
-    off += bwd_ws_layout(N, H, W, C, dtype).total;
+    w.blk = c.take(bwd_ws_layout(N, H, W, C, dtype).total);
   }
-  w.total = off;
+  w.total = c.off;
   return w;
+}
+
+// The C=64 stack kernel behind asr_block_stack_backward (xmids = masks2 = nullptr) and
+// asr_rk2_stack_backward: dyL into the kernel's ping-pong pair, one launch for all L blocks,
+// dx0 out, then the slab passes the launch left over and the projection onto theta.
+static int stack64_backward(const char* who, const StackWs& Lw, const void* dyL, const void* xs, const void* xmids,
+                            long x_stride, const uint8_t* masks, const uint8_t* masks2, long mask_stride,
+                            const void* w, long w_stride, const int32_t* theta_dst, long n_theta, float h, float gamma,
+                            int N, int H, int W, int C, int L, void* dx0, float* dparams, unsigned char* base,
+                            hipStream_t s) {
+  if (n_theta > 9L * C * C) return fail(ASR_E_ARG, "%s: n_theta > 9*C*C", who);
+  const size_t act = (size_t)N * H * W * C * 2;
+  ASR_TRY(hip_check(hipMemcpyAsync(base + Lw.da, dyL, act, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync"));
+  float* slabs = (float*)(base + Lw.slabs);
+  float* grp = (float*)(base + Lw.grp);
+  // the stack ABI's operator is antisymmetric (its dgrad is A^T = -A + 2 gamma I): pair-local slabs
+  const long ES = stack_slab_floats(C, 1), sst = (long)Lw.grid * ES, gst = (long)reduce_groups(Lw.grid) * ES;
+  int lfold = L;
+  ASR_TRY(block_stack_bwd_mfma(base + Lw.da, base + Lw.db, xs, x_stride, masks, mask_stride, w, w_stride, h,
+                               2.f * gamma, N, H, W, C, L, 0, slabs, sst, grp, gst, (unsigned*)(base + Lw.done),
+                               &lfold, s, xmids, masks2, xmids ? base + Lw.g : nullptr, nullptr, 1, 1));
+  ASR_TRY(hip_check(hipMemcpyAsync(dx0, base + ((L & 1) ? Lw.db : Lw.da), act, hipMemcpyDeviceToDevice, s),
+                    "hipMemcpyAsync"));
+  if (!dparams) return ASR_OK;
+  ASR_TRY(stack_bwd_reduce_rest(slabs, sst, Lw.grid, ES, grp, gst, L, lfold, (const unsigned*)(base + Lw.done), s));
+  int32_t* tm = (int32_t*)(base + Lw.tdst);
+  ASR_TRY(theta_dst_pair(theta_dst, n_theta, C, tm, s));
+  return project_layers(grp, gst, reduce_groups(Lw.grid), ES - C, C, tm, n_theta, L, dparams, n_theta + C, s);
 }
 
 size_t asr_block_stack_backward_workspace_bytes(int N, int H, int W, int C, int L, int dtype) {
@@ -702,86 +763,41 @@ int asr_block_stack_backward(const void* dyL, const void* xs, long x_stride, con
   if (!dyL || !xs || !masks || !w || !dx0 || L < 1) return fail(ASR_E_ARG, "asr_block_stack_backward: null pointer");
   if (dparams && !theta_dst) return fail(ASR_E_ARG, "asr_block_stack_backward: theta_dst needed for dparams");
   if (dtype != ASR_F32 && dtype != ASR_BF16) return fail(ASR_E_ARG, "asr_block_stack_backward: bad dtype");
-  if (dtype == ASR_BF16 && !mfma_supported(C, W) && !convb_supported(W, C))
-    return fail(ASR_E_UNSUPPORTED, "bf16 conv needs C in {16,32,64} and W in {32, 16, 8} (C=%d W=%d)", C, W);
+  if (dtype == ASR_BF16) ASR_TRY(check_bf16_conv(C, W));
   const StackWs Lw = stack_ws_layout(N, H, W, C, L, dtype);
-  if (Lw.img) ASR_TRY(stack_img_check_strides("asr_block_stack_backward", dtype, 0, 0, w_stride, 0, x_stride));
+  if (Lw.fused == kFusedImg)
+    ASR_TRY(stack_img_check_strides("asr_block_stack_backward", dtype, 0, 0, w_stride, 0, x_stride));
   if (!ws || ws_bytes < Lw.total) return fail(ASR_E_WORKSPACE, "asr_block_stack_backward: workspace too small");
+  if (Lw.fused == kFusedDeep16 && w_stride != (long)asr_wpack_elems(C))
+    return fail(ASR_E_ARG, "asr_block_stack_backward: w_stride must be asr_wpack_elems(C) on the fused path");
   hipStream_t s = (hipStream_t)stream;
   unsigned char* base = (unsigned char*)ws;
   const size_t es = dtype == ASR_BF16 ? 2 : 4, act = (size_t)N * H * W * C * es;
-  const long E = 9L * C * C;
-  if (Lw.img) {  // input gradients in one launch (a workgroup per image), then every layer's weight gradient in one
-    const long P = (long)N * H * W * C, sst = (long)Lw.rows * (E + C), gst = (long)reduce_groups(Lw.rows) * (E + C);
-    float* slabs = (float*)(base + Lw.slabs);
-    float* grp = (float*)(base + Lw.grp);
-    int nsl = 0;
-    if (dtype == ASR_BF16) {
-      ASR_TRY(stage_img_backward(dyL, base + Lw.dys, P, dx0, masks, mask_stride, w, w_stride, h, 2.f * gamma, N, H, W,
-                                 C, L, s));
-      if (dparams)
-        ASR_TRY(wgradb_layers(xs, x_stride, base + Lw.dys, P, masks, mask_stride, h, N, H, W, C, L, slabs, sst, &nsl, s));
-    } else {
-      ASR_TRY(stage_img32_backward((const float*)dyL, (float*)(base + Lw.dys), P, (float*)dx0, masks, mask_stride,
-                                   (const float*)w, w_stride, h, 2.f * gamma, N, H, W, C, L, s));
-      if (dparams)
-        ASR_TRY(wgrad32_layers((const float*)xs, x_stride, (const float*)(base + Lw.dys), P, masks, mask_stride, h, N,
-                               H, W, C, L, slabs, sst, &nsl, s));
-    }
-    if (!dparams) return ASR_OK;
-    if (nsl > Lw.rows)
-      return fail(ASR_E_WORKSPACE, "asr_block_stack_backward: %d slab rows > the workspace's %d", nsl, Lw.rows);
-    ASR_TRY(reduce_slab_layers(slabs, sst, nsl, E + C, grp, gst, L, s));
-    return project_layers(grp, gst, reduce_groups(nsl), E, C, theta_dst, n_theta, L, dparams, n_theta + C, s);
+  if (Lw.fused != kFusedNone) {
+    // the image-resident kernel reads dyL and writes dx0; deep16 ping-pongs in the workspace pair (dyL copied in,
+    // dx0 copied out by the shared function)
+    const bool deep = Lw.fused == kFusedDeep16;
+    const long ES = 9L * C * C + C;
+    if (deep) ASR_TRY(hip_check(hipMemcpyAsync(base + Lw.da, dyL, act, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync"));
+    int in_e = 0;
+    return fused_stage_backward("asr_block_stack_backward", Lw.fused, dtype, deep ? base + Lw.da : (void*)dyL,
+                                deep ? base + Lw.db : dx0, &in_e, deep ? dx0 : nullptr, base + Lw.dys, xs, x_stride,
+                                masks, mask_stride, w, w_stride, h, 2.f * gamma, N, H, W, C, L,
+                                (float*)(base + Lw.slabs), (long)Lw.rows * ES, Lw.rows, (float*)(base + Lw.grp),
+                                (long)reduce_groups(Lw.rows) * ES, theta_dst, n_theta, dparams, n_theta + C, s);
   }
-  if (Lw.deep) {
-    if (w_stride != (long)asr_wpack_elems(C))
-      return fail(ASR_E_ARG, "asr_block_stack_backward: w_stride must be asr_wpack_elems(C) on the fused path");
-    ASR_TRY(hip_check(hipMemcpyAsync(base + Lw.da, dyL, act, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync"));
-    int rows = 0, in_b = 0;
-    float* slabs = (float*)(base + Lw.slabs);
-    ASR_TRY(deep16_backward(base + Lw.da, base + Lw.db, xs, x_stride, masks, mask_stride, w, h, 2.f * gamma, N, L,
-                            slabs, &rows, &in_b, s));
-    ASR_TRY(hip_check(hipMemcpyAsync(dx0, base + (in_b ? Lw.db : Lw.da), act, hipMemcpyDeviceToDevice, s),
-                      "hipMemcpyAsync"));
-    if (dparams) {
-      const int G = reduce_groups(rows);
-      ASR_TRY(reduce_slabs_to_groups(slabs, L * rows, E + C, (float*)(base + Lw.grp), s));
-      ASR_TRY(project_layers((float*)(base + Lw.grp), (long)G * (E + C), G, E, C, theta_dst, n_theta, L, dparams,
-                             n_theta + C, s));
-    }
-    return ASR_OK;
-  }
-  if (Lw.stack64) {
-    if (n_theta > 9L * C * C) return fail(ASR_E_ARG, "asr_block_stack_backward: n_theta > 9*C*C");
-    ASR_TRY(hip_check(hipMemcpyAsync(base + Lw.da, dyL, act, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync"));
-    float* slabs = (float*)(base + Lw.slabs);
-    float* grp = (float*)(base + Lw.grp);
-    // the stack ABI's operator is antisymmetric (its dgrad is A^T = -A + 2 gamma I): pair-local slabs
-    const long ES = stack_slab_floats(C, 1), sst = (long)Lw.grid * ES, gst = (long)reduce_groups(Lw.grid) * ES;
-    int lfold = L;
-    ASR_TRY(block_stack_bwd_mfma(base + Lw.da, base + Lw.db, xs, x_stride, masks, mask_stride, w, w_stride, h,
-                                 2.f * gamma, N, H, W, C, L, 0, slabs, sst, grp, gst, (unsigned*)(base + Lw.done),
-                                 &lfold, s, nullptr, nullptr, nullptr, nullptr, 1, 1));
-    ASR_TRY(hip_check(hipMemcpyAsync(dx0, base + ((L & 1) ? Lw.db : Lw.da), act, hipMemcpyDeviceToDevice, s),
-                      "hipMemcpyAsync"));
-    if (dparams) {
-      ASR_TRY(stack_bwd_reduce_rest(slabs, sst, Lw.grid, ES, grp, gst, L, lfold, (const unsigned*)(base + Lw.done), s));
-      int32_t* tm = (int32_t*)(base + Lw.tdst);
-      ASR_TRY(theta_dst_pair(theta_dst, n_theta, C, tm, s));
-      ASR_TRY(project_layers(grp, gst, reduce_groups(Lw.grid), ES - C, C, tm, n_theta, L, dparams, n_theta + C, s));
-    }
-    return ASR_OK;
-  }
+  if (Lw.stack64)
+    return stack64_backward("asr_block_stack_backward", Lw, dyL, xs, nullptr, x_stride, masks, nullptr, mask_stride, w,
+                            w_stride, theta_dst, n_theta, h, gamma, N, H, W, C, L, dx0, dparams, base, s);
   // per-block kernels, last block first
   const void* dcur = dyL;
   for (int l = L - 1; l >= 0; --l) {
     void* dnext = l == 0 ? dx0 : base + ((l & 1) ? Lw.db : Lw.da);
     float* dp = dparams ? dparams + (long)l * (n_theta + C) : nullptr;
-    ASR_TRY(conv_backward_impl(ASR_MODE_EULER, dcur, (const unsigned char*)xs + (size_t)l * x_stride * es,
-                               masks + (size_t)l * mask_stride, (const unsigned char*)w + (size_t)l * w_stride * es,
-                               theta_dst, n_theta, h, gamma, N, H, W, C, dtype, dnext, dp, dp ? dp + n_theta : nullptr,
-                               nullptr, base + Lw.blk, s));
+    ASR_TRY(asr_conv_backward(ASR_MODE_EULER, dcur, (const unsigned char*)xs + (size_t)l * x_stride * es,
+                              masks + (size_t)l * mask_stride, (const unsigned char*)w + (size_t)l * w_stride * es,
+                              theta_dst, n_theta, h, gamma, N, H, W, C, dtype, dnext, dp, dp ? dp + n_theta : nullptr,
+                              nullptr, base + Lw.blk, ws_bytes - Lw.blk, stream));
     dcur = dnext;
   }
   return ASR_OK;
@@ -817,27 +833,9 @@ int asr_rk2_stack_backward(const void* dyL, const void* xs, const void* xmids, l
   const StackWs Lw = stack_ws_layout(N, H, W, C, L, dtype, true);
   if (!Lw.stack64) return fail(ASR_E_UNSUPPORTED, "asr_rk2_stack_backward: bf16, C=64, W=32 only (C=%d W=%d)", C, W);
   if (!ws || ws_bytes < Lw.total) return fail(ASR_E_WORKSPACE, "asr_rk2_stack_backward: workspace too small");
-  if (n_theta > 9L * C * C) return fail(ASR_E_ARG, "asr_rk2_stack_backward: n_theta > 9*C*C");
-  hipStream_t s = (hipStream_t)stream;
-  unsigned char* base = (unsigned char*)ws;
-  const size_t act = (size_t)N * H * W * C * 2;
-  const long ES = stack_slab_floats(C, 1), sst = (long)Lw.grid * ES, gst = (long)reduce_groups(Lw.grid) * ES;
-  ASR_TRY(hip_check(hipMemcpyAsync(base + Lw.da, dyL, act, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync"));
-  float* slabs = (float*)(base + Lw.slabs);
-  float* grp = (float*)(base + Lw.grp);
-  int lfold = L;
-  ASR_TRY(block_stack_bwd_mfma(base + Lw.da, base + Lw.db, xs, x_stride, masks1, mask_stride, w, w_stride, h,
-                               2.f * gamma, N, H, W, C, L, 0, slabs, sst, grp, gst, (unsigned*)(base + Lw.done),
-                               &lfold, s, xmids, masks2, base + Lw.g, nullptr, 1, 1));
-  ASR_TRY(hip_check(hipMemcpyAsync(dx0, base + ((L & 1) ? Lw.db : Lw.da), act, hipMemcpyDeviceToDevice, s),
-                    "hipMemcpyAsync"));
-  if (dparams) {
-    ASR_TRY(stack_bwd_reduce_rest(slabs, sst, Lw.grid, ES, grp, gst, L, lfold, (const unsigned*)(base + Lw.done), s));
-    int32_t* tm = (int32_t*)(base + Lw.tdst);
-    ASR_TRY(theta_dst_pair(theta_dst, n_theta, C, tm, s));
-    ASR_TRY(project_layers(grp, gst, reduce_groups(Lw.grid), ES - C, C, tm, n_theta, L, dparams, n_theta + C, s));
-  }
-  return ASR_OK;
+  return stack64_backward("asr_rk2_stack_backward", Lw, dyL, xs, xmids, x_stride, masks1, masks2, mask_stride, w,
+                          w_stride, theta_dst, n_theta, h, gamma, N, H, W, C, L, dx0, dparams, (unsigned char*)ws,
+                          (hipStream_t)stream);
 }
 
 size_t asr_conv_backward_workspace_bytes_k(int N, int H, int W, int C, int kernel_size) {
@@ -853,8 +851,7 @@ int asr_conv_forward_k(int mode, int kernel_size, const float* x, float* y, uint
   ASR_TRY(check_shape(N, H, W, C));
   if (!x || !y || !w) return fail(ASR_E_ARG, "asr_conv_forward_k: null pointer");
   if (mode != ASR_MODE_EULER && mode != ASR_MODE_CONV) return fail(ASR_E_ARG, "asr_conv_forward_k: bad mode %d", mode);
-  if (kernel_size < 1 || kernel_size > 15 || !(kernel_size & 1))
-    return fail(ASR_E_ARG, "asr_conv_forward_k: kernel_size %d (odd, 1..15)", kernel_size);
+  ASR_TRY(check_kernel_size("asr_conv_forward_k", kernel_size));
   return conv_f32_k(mode == ASR_MODE_EULER ? F_EULER : F_CONV, kernel_size, x, y, mask, w, bias, h, 0.f, nullptr, N, H, W,
                     C, (hipStream_t)stream, nullptr);
 }
@@ -865,8 +862,7 @@ int asr_conv_backward_k(int mode, int kernel_size, const float* dy, const float*
                         asr_stream_t stream) {
   ASR_TRY(check_shape(N, H, W, C));
   if (mode != ASR_MODE_EULER && mode != ASR_MODE_CONV) return fail(ASR_E_ARG, "asr_conv_backward_k: bad mode %d", mode);
-  if (kernel_size < 1 || kernel_size > 15 || !(kernel_size & 1))
-    return fail(ASR_E_ARG, "asr_conv_backward_k: kernel_size %d (odd, 1..15)", kernel_size);
+  ASR_TRY(check_kernel_size("asr_conv_backward_k", kernel_size));
   if (!dy || !w || (mode == ASR_MODE_EULER && !mask)) return fail(ASR_E_ARG, "asr_conv_backward_k: null pointer");
   if ((dtheta || dbias || dw) && !x) return fail(ASR_E_ARG, "asr_conv_backward_k: x needed for weight gradients");
   if (dtheta && !theta_dst) return fail(ASR_E_ARG, "asr_conv_backward_k: theta_dst needed for dtheta");
@@ -892,8 +888,7 @@ int asr_conv_backward_k(int mode, int kernel_size, const float* dy, const float*
 // The same layer in bf16 (fp32 accumulation) on the matrix cores (asr_conv_kxk.hip), for
 // kernel_size in {5, 7}, C in {16, 32, 64}, W in {8, 16, 32}; w: asr_theta_to_w_k_bf16's pack.
 static int check_k_bf16(const char* fn, int kernel_size, int W, int C) {
-  if (kernel_size < 1 || kernel_size > 15 || !(kernel_size & 1))
-    return fail(ASR_E_ARG, "%s: kernel_size %d (odd, 1..15)", fn, kernel_size);
+  ASR_TRY(check_kernel_size(fn, kernel_size));
   if (!convk_bf16_supported(kernel_size, W, C))
     return fail(ASR_E_UNSUPPORTED,
                 "%s: the bf16 k x k kernels take kernel_size in {5, 7}, C in {16, 32, 64}, W in {8, 16, 32} "
@@ -910,9 +905,10 @@ static BwdWsK bwd_ws_layout_k_bf16(int N, int H, int W, int C, int K) {
   BwdWsK b{};
   const long ES = (long)K * K * C * C + C;
   b.rows = wgradk_bf16_slab_rows(K, N, H, W, C);
-  b.slabs = 0;
-  b.red = align_up((size_t)b.rows * ES * 4, 256);
-  b.total = b.red + align_up(reduce_ws_bytes(b.rows, ES), 256);
+  WsCursor c;
+  b.slabs = c.take((size_t)b.rows * ES * 4);
+  b.red = c.take(reduce_ws_bytes(b.rows, ES));
+  b.total = c.off;
   return b;
 }
 
@@ -975,13 +971,20 @@ int asr_conv_backward(int mode, const void* dy, const void* x, const uint8_t* ma
   if ((dtheta || dbias || dw_hwio) && !x) return fail(ASR_E_ARG, "asr_conv_backward: x needed for weight gradients");
   if (dtheta && !theta_dst) return fail(ASR_E_ARG, "asr_conv_backward: theta_dst needed for dtheta");
   if (dtype != ASR_F32 && dtype != ASR_BF16) return fail(ASR_E_ARG, "asr_conv_backward: bad dtype");
-  if (dtype == ASR_BF16 && !mfma_supported(C, W) && !convb_supported(W, C))
-    return fail(ASR_E_UNSUPPORTED, "bf16 conv needs C in {16,32,64} and W in {32, 16, 8} (C=%d W=%d)",
-                C, W);
-  if (!ws || ws_bytes < bwd_ws_layout(N, H, W, C, dtype).total)
-    return fail(ASR_E_WORKSPACE, "asr_conv_backward: workspace too small");
-  return conv_backward_impl(mode, dy, x, mask, w, theta_dst, n_theta, h, gamma, N, H, W, C, dtype, dx, dtheta, dbias,
-                            dw_hwio, ws, (hipStream_t)stream);
+  if (dtype == ASR_BF16) ASR_TRY(check_bf16_conv(C, W));
+  const BwdWs L = bwd_ws_layout(N, H, W, C, dtype);
+  if (!ws || ws_bytes < L.total) return fail(ASR_E_WORKSPACE, "asr_conv_backward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* base = (unsigned char*)ws;
+  float* slabs = (float*)(base + L.slabs);
+  const bool need_w = dtheta || dbias || dw_hwio;
+  int nsl = 0;
+  ASR_TRY(block_backward(mode, dy, x, mask, w, h, gamma, N, H, W, C, dtype, dx, need_w, nullptr, false, slabs,
+                         (float*)(base + L.dz), &nsl, s));
+  if (need_w)
+    ASR_TRY(reduce_and_project(slabs, nsl, 9L * C * C, C, dtheta ? theta_dst : nullptr, n_theta, dtheta, dbias,
+                               dw_hwio, (float*)(base + L.red), s));
+  return ASR_OK;
 }
 
 static int check_block_args(const char* fn, int N, int H, int W, int C, int dtype) {
@@ -1058,7 +1061,8 @@ int asr_net_prepare(const asr_net_config* cfg, void* ws, size_t ws_bytes) {
     ASR_TRY(theta_dst_pair_host(theta_dst.data(), L.ntheta, cfg->C, pr.data()));
     ASR_TRY(hip_check(hipMemcpy(b + L.theta_dst_pr, pr.data(), pr.size() * 4, hipMemcpyHostToDevice), "hipMemcpy"));
   }
-  if (L.stack_bwd) {  // the same map into k_bwd3_stack's tile-major dW slabs (ASR_VARIANT_FULL_SLABS)
+  if (L.stack_bwd) {  // the same map into k_bwd3_stack's tile-major dW slabs (ASR_VARIANT_FULL_SLABS):
+    // entry e = m*C + o of the row-major dW -> ((m/16 * C/16 + o/16) * 64 + 16*((m%16)/4) + o%16) * 4 + m%4
     const int C = cfg->C;
     std::vector<int32_t> tm(theta_dst);
     for (auto& v : tm) {
@@ -1150,7 +1154,6 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
   // blocks, last to first
   const int32_t* theta_dst = (const int32_t*)(b + L.theta_dst);
   int nsl_blk = 0;
-  const BwdWs bw = bwd_ws_layout(N, H, W, C, cfg->dtype, L.stages, 3, bf ? -1 : 0);  // (net_layout's)
   int dz1_fused = 0;  // dcur holds dz1 = dx1 * [x1 > 0] after the block loop
   const float* pend_slabs = nullptr;  // the slabs whose pass-1 reduction is still pending
   int pend_P = 0;
@@ -1159,6 +1162,7 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
   const bool stem_v1 = (cfg->variant & ASR_VARIANT_STEM_WGRAD_VALU) != 0;  // fp32 VALU stem wgrad
   ASR_TRY(timed_event(cfg, 2, s));  // (measurement) the blocks' backward starts
   if (L.deep) {  // C=16: all L blocks in one launch (dx resident in LDS), one slab set per layer
+    // (fused_stage_backward's deep16 sequence written out: timed event 3 sits between the kernel and its reductions)
     int rows = 0, in_b = 0;
     float* slabs = (float*)(b + L.deep_slabs);
     ASR_TRY(deep16_backward(dcur, dnext, act(0), L.P, (const uint8_t*)(b + L.masks), L.mask_bytes,
@@ -1211,16 +1215,16 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
     // block (or the end of the loop)
     // (fp32: every block keeps its own slabs; one launch reduces them all after the loop)
     float* slabs_l = !bf ? (float*)(b + L.slabs_all) + (size_t)l * L.slab_stride
-                         : (float*)(b + ((l & 1) ? L.slabs2 : L.bwdws + bw.slabs));
+                         : (float*)(b + ((l & 1) ? L.slabs2 : L.bwdws + L.bw.slabs));
     int nsl = 0, folded = 0;
     if (L.rk2) {
       const unsigned char* xm = b + L.xmids + (size_t)l * L.P * L.act_bytes;
       ASR_TRY(rk2_backward_slabs(dcur, act(l), xm, mask, mask + (size_t)cfg->L * L.mask_bytes, wl, cfg->h, gam, N, H,
-                                 W, C, cfg->dtype, dnext, b + L.dxg, true, slabs_l, (float*)(b + L.bwdws + bw.dz),
+                                 W, C, cfg->dtype, dnext, b + L.dxg, true, slabs_l, (float*)(b + L.bwdws + L.bw.dz),
                                  &nsl, s, fold_on ? pend_slabs : nullptr, fold_on ? pend_P : 0, pend_grp, &folded));
     } else {
       ASR_TRY(block_backward(ASR_MODE_EULER, dcur, act(l), mask, wl, cfg->h, gam, N, H, W, C, cfg->dtype, dnext, true,
-                             nullptr, false, slabs_l, (float*)(b + L.bwdws + bw.dz), &nsl, s,
+                             nullptr, false, slabs_l, (float*)(b + L.bwdws + L.bw.dz), &nsl, s,
                              l == 0 && L.fast_stem && bf && !stem_v1, l == 0 ? &dz1_fused : nullptr,
                              fold_on ? pend_slabs : nullptr, fold_on ? pend_P : 0, pend_grp, &folded));
     }
@@ -1250,17 +1254,13 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
   }
   // stem: dz1 = dx1 * [x1 > 0]; conv1 weight/bias gradient from the normalised input
   const long E1 = 9L * cfg->Cin * C;
-  unsigned char* sw = b + L.bwdws;
-  float* dz = (float*)sw;
-  float* slabs = (float*)(sw + align_up((size_t)L.P * 4, 256));
-  float* red = (float*)(sw + align_up((size_t)L.P * 4, 256) + align_up((size_t)kMaxBlockSlabs * (E1 + C) * 4, 256));
+  float* dz = (float*)(b + L.bwdws + L.stem.dz);
+  float* slabs = (float*)(b + L.bwdws + L.stem.slabs);
+  float* red = (float*)(b + L.bwdws + L.stem.red);
   int nsl = 0;
   const float inv_std = cfg->use_norm ? 1.f / cfg->divide_by_stddev : 1.f;
   if (L.fast_stem && bf && !dz1_fused && !stem_v1 && stem_wgrad_mfma_supported(cfg->Cin, H, W, C) && L.P % 8 == 0) {
-    const long n8 = (long)L.P / 8;
-    hipLaunchKernelGGL(k_relu_grad_bf16, dim3((unsigned)std::min<long>((n8 + 255) / 256, 4096)), dim3(256), 0, s,
-                       (bf16*)dcur, (const bf16*)act(0), n8);
-    ASR_LAUNCH_CHECK("k_relu_grad_bf16");
+    ASR_TRY(relu_grad_bf16(dcur, act(0), L.P, s));
     dz1_fused = 1;
   }
   if (L.fast_stem && dz1_fused && stem_wgrad_mfma_supported(cfg->Cin, H, W, C)) {

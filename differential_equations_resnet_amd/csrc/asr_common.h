@@ -36,6 +36,17 @@ inline int hip_check(hipError_t e, const char* what) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Cursor of a workspace layout: take(bytes) is the next buffer's offset; the
+// one after it starts 256-B aligned.  `off` ends as the layout's total.
+struct WsCursor {
+  size_t off = 0;
+  size_t take(size_t bytes) {
+    const size_t o = off;
+    off += align_up(bytes, 256);
+    return o;
+  }
+};
+
 // One launch of the balanced bf16 weight pack for several layer sets (the
 // multi-stage net's stages, asr_stages.hip): one workgroup per layer, so the
 // stages' packs run side by side (theta_to_w_bf16_jobs, asr_internal.h;

@@ -1575,118 +1575,106 @@ __global__ __launch_bounds__((StImg32<C, W>::NTH)) void k_stageb32(const float* 
   }
 }
 
-bool stage_img32_supported(int H, int W, int C) { return H == W && ((W == 16 && C == 32) || (W == 8 && C == 64)); }
-
-int stage_img32_forward(const float* x0, float* ys, long y_stride, uint8_t* masks, long mask_stride, const float* w,
-                        long w_stride, const float* bias, long bias_stride, float h, int N, int H, int W, int C, int L,
-                        hipStream_t s) {
-  if (!stage_img32_supported(H, W, C)) return fail(ASR_E_UNSUPPORTED, "fp32 image-resident stage: H=%d W=%d C=%d", H, W, C);
-  const unsigned grid = (unsigned)std::max(1, N);
-#define ASR_SF32(CC, WW)                                                                                             \
-  if (C == CC && W == WW) {                                                                                          \
-    using GG = StImg32<CC, WW>;                                                                                      \
-    const size_t lds = (size_t)2 * GG::IMGF * 4;                                                                     \
-    hipLaunchKernelGGL((k_stagef32<CC, WW>), dim3(grid), dim3(GG::NTH), lds, s, x0, ys, y_stride, masks, mask_stride, w, \
-                       w_stride, bias, bias_stride, h, N, L);                                                        \
-    ASR_LAUNCH_CHECK("k_stagef32");                                                                                  \
-    return ASR_OK;                                                                                                   \
-  }
-  ASR_SF32(32, 16) ASR_SF32(64, 8)
-#undef ASR_SF32
-  return fail(ASR_E_UNSUPPORTED, "fp32 image-resident stage: C=%d W=%d", C, W);
+// The image-resident stages behind one interface: dtype picks k_stagef / k_stageb / k_wgradb (ASR_BF16) or
+// k_stagef32 / k_stageb32 / k_wgrad32 (ASR_F32), and every activation / W pointer is of that type.
+bool stage_img_supported(int H, int W, int C, int dtype) {
+  if (H != W) return false;
+  if (dtype == ASR_BF16) return (W == 16 && C == 32) || (W == 8 && C == 64) || (W == 8 && C == 32);
+  return dtype == ASR_F32 && ((W == 16 && C == 32) || (W == 8 && C == 64));
 }
-
-int stage_img32_backward(const float* dyL, float* dys, long d_stride, float* dx0, const uint8_t* masks,
-                         long mask_stride, const float* w, long w_stride, float h, float two_gamma, int N, int H, int W,
-                         int C, int L, hipStream_t s) {
-  if (!stage_img32_supported(H, W, C)) return fail(ASR_E_UNSUPPORTED, "fp32 image-resident stage: H=%d W=%d C=%d", H, W, C);
-  const unsigned grid = (unsigned)std::max(1, N);
-#define ASR_SB32(CC, WW)                                                                                            \
-  if (C == CC && W == WW) {                                                                                         \
-    using GG = StImg32<CC, WW>;                                                                                     \
-    const size_t lds = (size_t)(GG::IMGF + GG::H * WW * GG::PS) * 4;                                                \
-    hipLaunchKernelGGL((k_stageb32<CC, WW>), dim3(grid), dim3(GG::NTH), lds, s, dyL, dys, d_stride, dx0, masks,     \
-                       mask_stride, w, w_stride, h, two_gamma, N, L);                                               \
-    ASR_LAUNCH_CHECK("k_stageb32");                                                                                 \
-    return ASR_OK;                                                                                                  \
-  }
-  ASR_SB32(32, 16) ASR_SB32(64, 8)
-#undef ASR_SB32
-  return fail(ASR_E_UNSUPPORTED, "fp32 image-resident stage: C=%d W=%d", C, W);
-}
-
-// every layer's fp32 weight-gradient slabs in one launch (k_wgrad32, blockIdx.y = layer)
-int wgrad32_layers(const float* x0, long x_stride, const float* dys, long d_stride, const uint8_t* masks,
-                   long mask_stride, float h, int N, int H, int W, int C, int L, float* slabs, long slab_stride,
-                   int* nslabs, hipStream_t s) {
-#define ASR_W32L(CC, WW)                                                                                     \
-  if (C == CC && W == WW)                                                                                    \
-    return launch_wgrad32<CC, WW>(x0, dys, N, H, slabs, nslabs, s, masks, h, L, x_stride, d_stride, mask_stride, \
-                                  slab_stride);
-  ASR_W32L(32, 16) ASR_W32L(64, 8) ASR_W32L(16, 32) ASR_W32L(32, 32) ASR_W32L(64, 16)
-#undef ASR_W32L
-  return fail(ASR_E_UNSUPPORTED, "fp32 weight gradient (layers): C=%d W=%d", C, W);
-}
-
-bool stage_img_supported(int H, int W, int C) {
-  return H == W && ((W == 16 && C == 32) || (W == 8 && C == 64) || (W == 8 && C == 32));
+static const char* stage_img_name(int dtype) {
+  return dtype == ASR_BF16 ? "image-resident stage" : "fp32 image-resident stage";
 }
 
 // the image-resident stage forward: x0 [N][H][W][C] -> ys (L layers at y_stride), masks (L at mask_stride)
-int stage_img_forward(const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride, const void* w,
-                      long w_stride, const float* bias, long bias_stride, float h, int N, int H, int W, int C, int L,
-                      hipStream_t s) {
-  if (!stage_img_supported(H, W, C)) return fail(ASR_E_UNSUPPORTED, "image-resident stage: H=%d W=%d C=%d", H, W, C);
-  const unsigned grid = (unsigned)std::max(1, (N + kStIpw - 1) / kStIpw);
+int stage_img_forward(int dtype, const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride,
+                      const void* w, long w_stride, const float* bias, long bias_stride, float h, int N, int H, int W,
+                      int C, int L, hipStream_t s) {
+  if (!stage_img_supported(H, W, C, dtype))
+    return fail(ASR_E_UNSUPPORTED, "%s: H=%d W=%d C=%d", stage_img_name(dtype), H, W, C);
+  const bool bf = dtype == ASR_BF16;
 #define ASR_SF(CC, WW)                                                                                        \
-  if (C == CC && W == WW) {                                                                                   \
-    const size_t lds = (size_t)kStIpw * 2 * StImg<CC, WW>::IMGE * 2;                                      \
-    hipLaunchKernelGGL((k_stagef<CC, WW>), dim3(grid), dim3(StImg<CC, WW>::NTH), lds, s, (const bf16*)x0, (bf16*)ys, \
-                       y_stride,                                                                              \
-                       masks, mask_stride, (const bf16*)w, w_stride, bias, bias_stride, h, N, L);             \
+  if (bf && C == CC && W == WW) {                                                                             \
+    const unsigned grid = (unsigned)std::max(1, (N + kStIpw - 1) / kStIpw);                                   \
+    const size_t lds = (size_t)kStIpw * 2 * StImg<CC, WW>::IMGE * 2;                                          \
+    hipLaunchKernelGGL((k_stagef<CC, WW>), dim3(grid), dim3(StImg<CC, WW>::NTH), lds, s, (const bf16*)x0,     \
+                       (bf16*)ys, y_stride, masks, mask_stride, (const bf16*)w, w_stride, bias, bias_stride, h, N, \
+                       L);                                                                                    \
     ASR_LAUNCH_CHECK("k_stagef");                                                                             \
     return ASR_OK;                                                                                            \
   }
-  ASR_SF(32, 16) ASR_SF(64, 8)
-  ASR_SF(32, 8)
+#define ASR_SF32(CC, WW)                                                                                      \
+  if (!bf && C == CC && W == WW) {                                                                            \
+    using GG = StImg32<CC, WW>;                                                                               \
+    const size_t lds = (size_t)2 * GG::IMGF * 4;                                                              \
+    hipLaunchKernelGGL((k_stagef32<CC, WW>), dim3((unsigned)std::max(1, N)), dim3(GG::NTH), lds, s,           \
+                       (const float*)x0, (float*)ys, y_stride, masks, mask_stride, (const float*)w, w_stride, bias, \
+                       bias_stride, h, N, L);                                                                 \
+    ASR_LAUNCH_CHECK("k_stagef32");                                                                           \
+    return ASR_OK;                                                                                            \
+  }
+  ASR_SF(32, 16) ASR_SF(64, 8) ASR_SF(32, 8)
+  ASR_SF32(32, 16) ASR_SF32(64, 8)
 #undef ASR_SF
-  return fail(ASR_E_UNSUPPORTED, "image-resident stage: C=%d W=%d", C, W);
+#undef ASR_SF32
+  return fail(ASR_E_UNSUPPORTED, "%s: C=%d W=%d", stage_img_name(dtype), C, W);
 }
 
 // its backward (input gradient): dyL -> dx0; dys: the gradient entering each layer 0 .. L-1 (d_stride apart)
-int stage_img_backward(const void* dyL, void* dys, long d_stride, void* dx0, const uint8_t* masks, long mask_stride,
-                       const void* w, long w_stride, float h, float two_gamma, int N, int H, int W, int C, int L,
-                       hipStream_t s) {
-  if (!stage_img_supported(H, W, C)) return fail(ASR_E_UNSUPPORTED, "image-resident stage: H=%d W=%d C=%d", H, W, C);
-  const unsigned grid = (unsigned)std::max(1, (N + kStIpw - 1) / kStIpw);
-#define ASR_SB(CC, WW)                                                                                           \
-  if (C == CC && W == WW) {                                                                                      \
-    using GG = StImg<CC, WW>;                                                                                    \
-    const size_t lds = (size_t)kStIpw * (GG::IMGE + GG::H * WW * GG::PS) * 2;                                \
-    hipLaunchKernelGGL((k_stageb<CC, WW>), dim3(grid), dim3(GG::NTH), lds, s, (const bf16*)dyL, (bf16*)dys, d_stride, \
-                       (bf16*)dx0, masks, mask_stride, (const bf16*)w, w_stride, h, two_gamma, N, L);             \
-    ASR_LAUNCH_CHECK("k_stageb");                                                                                \
-    return ASR_OK;                                                                                               \
+int stage_img_backward(int dtype, const void* dyL, void* dys, long d_stride, void* dx0, const uint8_t* masks,
+                       long mask_stride, const void* w, long w_stride, float h, float two_gamma, int N, int H, int W,
+                       int C, int L, hipStream_t s) {
+  if (!stage_img_supported(H, W, C, dtype))
+    return fail(ASR_E_UNSUPPORTED, "%s: H=%d W=%d C=%d", stage_img_name(dtype), H, W, C);
+  const bool bf = dtype == ASR_BF16;
+#define ASR_SB(CC, WW)                                                                                        \
+  if (bf && C == CC && W == WW) {                                                                             \
+    using GG = StImg<CC, WW>;                                                                                 \
+    const unsigned grid = (unsigned)std::max(1, (N + kStIpw - 1) / kStIpw);                                   \
+    const size_t lds = (size_t)kStIpw * (GG::IMGE + GG::H * WW * GG::PS) * 2;                                 \
+    hipLaunchKernelGGL((k_stageb<CC, WW>), dim3(grid), dim3(GG::NTH), lds, s, (const bf16*)dyL, (bf16*)dys,   \
+                       d_stride, (bf16*)dx0, masks, mask_stride, (const bf16*)w, w_stride, h, two_gamma, N, L); \
+    ASR_LAUNCH_CHECK("k_stageb");                                                                             \
+    return ASR_OK;                                                                                            \
   }
-  ASR_SB(32, 16) ASR_SB(64, 8)
-  ASR_SB(32, 8)
+#define ASR_SB32(CC, WW)                                                                                      \
+  if (!bf && C == CC && W == WW) {                                                                            \
+    using GG = StImg32<CC, WW>;                                                                               \
+    const size_t lds = (size_t)(GG::IMGF + GG::H * WW * GG::PS) * 4;                                          \
+    hipLaunchKernelGGL((k_stageb32<CC, WW>), dim3((unsigned)std::max(1, N)), dim3(GG::NTH), lds, s,           \
+                       (const float*)dyL, (float*)dys, d_stride, (float*)dx0, masks, mask_stride, (const float*)w, \
+                       w_stride, h, two_gamma, N, L);                                                         \
+    ASR_LAUNCH_CHECK("k_stageb32");                                                                           \
+    return ASR_OK;                                                                                            \
+  }
+  ASR_SB(32, 16) ASR_SB(64, 8) ASR_SB(32, 8)
+  ASR_SB32(32, 16) ASR_SB32(64, 8)
 #undef ASR_SB
-  return fail(ASR_E_UNSUPPORTED, "image-resident stage: C=%d W=%d", C, W);
+#undef ASR_SB32
+  return fail(ASR_E_UNSUPPORTED, "%s: C=%d W=%d", stage_img_name(dtype), C, W);
 }
 
-// the weight-gradient slabs of L layers in one launch (k_wgradb, blockIdx.y = layer): layer l reads
+// the weight-gradient slabs of L layers in one launch (k_wgradb / k_wgrad32, blockIdx.y = layer): layer l reads
 // x0 + l x_stride, dys + l d_stride, masks + l mask_stride and writes slabs + l slab_stride
-int wgradb_layers(const void* x0, long x_stride, const void* dys, long d_stride, const uint8_t* masks,
-                  long mask_stride, float h, int N, int H, int W, int C, int L, float* slabs, long slab_stride,
-                  int* nslabs, hipStream_t s) {
+int wgrad_layers(int dtype, const void* x0, long x_stride, const void* dys, long d_stride, const uint8_t* masks,
+                 long mask_stride, float h, int N, int H, int W, int C, int L, float* slabs, long slab_stride,
+                 int* nslabs, hipStream_t s) {
+  const bool bf = dtype == ASR_BF16;
 #define ASR_WL(CC, WW)                                                                                              \
-  if (C == CC && W == WW)                                                                                           \
+  if (bf && C == CC && W == WW)                                                                                     \
     return launch_wgradb<CC, WW>((const bf16*)x0, (const bf16*)dys, masks, N, H, h, slabs, nslabs, s, L, x_stride, \
                                  d_stride, mask_stride, slab_stride);
+#define ASR_W32L(CC, WW)                                                                                            \
+  if (!bf && C == CC && W == WW)                                                                                    \
+    return launch_wgrad32<CC, WW>((const float*)x0, (const float*)dys, N, H, slabs, nslabs, s, masks, h, L, x_stride, \
+                                  d_stride, mask_stride, slab_stride);
   ASR_WL(16, 32) ASR_WL(16, 16) ASR_WL(16, 8) ASR_WL(32, 32) ASR_WL(32, 16) ASR_WL(32, 8) ASR_WL(64, 32)
   ASR_WL(64, 16) ASR_WL(64, 8)
+  ASR_W32L(32, 16) ASR_W32L(64, 8) ASR_W32L(16, 32) ASR_W32L(32, 32) ASR_W32L(64, 16)
 #undef ASR_WL
-  return fail(ASR_E_UNSUPPORTED, "bf16 weight gradient: C=%d W=%d", C, W);
+#undef ASR_W32L
+  if (bf) return fail(ASR_E_UNSUPPORTED, "bf16 weight gradient: C=%d W=%d", C, W);
+  return fail(ASR_E_UNSUPPORTED, "fp32 weight gradient (layers): C=%d W=%d", C, W);
 }
 
 // elementwise bf16 <-> fp32 (the multi-stage bf16 net's transitions run in fp32)

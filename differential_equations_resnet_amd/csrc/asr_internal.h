@@ -54,7 +54,6 @@ int reduce_slab_layers(const float* slabs, long slab_stride, int P, long ES, flo
                        hipStream_t s);
 int project_layers(float* grp, long grp_stride, int G, long E, int Cb, const int32_t* theta_dst, long n_theta,
                    int L, float* out, long out_stride, hipStream_t s);
-int theta_dst_tile_major(const int32_t* in, long n, int C, int32_t* out, hipStream_t s);
 int theta_dst_pair(const int32_t* in, long n_theta, int C, int32_t* out, hipStream_t s);
 int theta_dst_pair_host(const int32_t* in, long n_theta, int C, int32_t* out);
 
@@ -123,26 +122,17 @@ int convb_backward(const void* dy, const uint8_t* mask, const void* x, const voi
                    bool conv_only = false);
 // bf16 <-> fp32, the image-resident stages (all L blocks of a 16 x 16 x 32 or 8 x 8 x 64 stage in one launch)
 int convert_bf16_f32(const void* src, void* dst, long n, int to_f32, hipStream_t s);
-bool stage_img_supported(int H, int W, int C);
-int stage_img_forward(const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride, const void* w,
-                      long w_stride, const float* bias, long bias_stride, float h, int N, int H, int W, int C, int L,
-                      hipStream_t s);
-int stage_img_backward(const void* dyL, void* dys, long d_stride, void* dx0, const uint8_t* masks, long mask_stride,
-                       const void* w, long w_stride, float h, float two_gamma, int N, int H, int W, int C, int L,
-                       hipStream_t s);
-bool stage_img32_supported(int H, int W, int C);
-int stage_img32_forward(const float* x0, float* ys, long y_stride, uint8_t* masks, long mask_stride, const float* w,
-                        long w_stride, const float* bias, long bias_stride, float h, int N, int H, int W, int C, int L,
-                        hipStream_t s);
-int stage_img32_backward(const float* dyL, float* dys, long d_stride, float* dx0, const uint8_t* masks,
-                         long mask_stride, const float* w, long w_stride, float h, float two_gamma, int N, int H, int W,
-                         int C, int L, hipStream_t s);
-int wgrad32_layers(const float* x0, long x_stride, const float* dys, long d_stride, const uint8_t* masks,
-                   long mask_stride, float h, int N, int H, int W, int C, int L, float* slabs, long slab_stride,
-                   int* nslabs, hipStream_t s);
-int wgradb_layers(const void* x0, long x_stride, const void* dys, long d_stride, const uint8_t* masks,
-                  long mask_stride, float h, int N, int H, int W, int C, int L, float* slabs, long slab_stride,
-                  int* nslabs, hipStream_t s);
+// dtype (ASR_BF16 / ASR_F32) picks the kernels; activations, W and dys are of that type
+bool stage_img_supported(int H, int W, int C, int dtype);
+int stage_img_forward(int dtype, const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride,
+                      const void* w, long w_stride, const float* bias, long bias_stride, float h, int N, int H, int W,
+                      int C, int L, hipStream_t s);
+int stage_img_backward(int dtype, const void* dyL, void* dys, long d_stride, void* dx0, const uint8_t* masks,
+                       long mask_stride, const void* w, long w_stride, float h, float two_gamma, int N, int H, int W,
+                       int C, int L, hipStream_t s);
+int wgrad_layers(int dtype, const void* x0, long x_stride, const void* dys, long d_stride, const uint8_t* masks,
+                 long mask_stride, float h, int N, int H, int W, int C, int L, float* slabs, long slab_stride,
+                 int* nslabs, hipStream_t s);
 
 // ---- asr_conv_kxk.hip ------------------------------------------------------
 // bf16 Conv2DAntisymmetric(kernel_size = K), K in {5, 7}, C in {16, 32, 64}, W in {32, 16, 8}
@@ -179,5 +169,20 @@ int head_param_grads(const float* gap, const float* dlogits, int N, int C, int K
 int conv_backward_keep_slabs(const void* dy, const void* x, const uint8_t* mask, const void* w, float h, float gamma,
                              int N, int H, int W, int C, void* dx, void* ws, float* slabs, int* nsl, hipStream_t s);
 int relu_grad_bf16(void* d, const void* x, long n, hipStream_t s);
+// A stage whose L Euler blocks run in one launch: deep16 (bf16, 32 x 32 x 16) before the
+// image-resident kernels (stage_img_supported); the stack ABI and the multi-stage executor
+// run both through fused_stage_forward / fused_stage_backward.
+constexpr int kFusedNone = 0;
+constexpr int kFusedDeep16 = 1;
+constexpr int kFusedImg = 2;
+int fused_stage_kind(int H, int W, int C, int dtype);
+int fused_stage_forward(int kind, int dtype, const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride,
+                        const void* w, long w_stride, const float* bias, long bias_stride, float h, int N, int H, int W,
+                        int C, int L, bool store_all, hipStream_t s);
+int fused_stage_backward(const char* who, int kind, int dtype, void* d, void* e, int* in_e, void* dx0_copy, void* dys,
+                         const void* xs, long x_stride, const uint8_t* masks, long mask_stride, const void* w,
+                         long w_stride, float h, float two_gamma, int N, int H, int W, int C, int L, float* slabs,
+                         long slab_stride, int slab_rows, float* grp, long grp_stride, const int32_t* theta_dst,
+                         long n_theta, float* dparams, long dp_stride, hipStream_t s);
 
 }  // namespace asr

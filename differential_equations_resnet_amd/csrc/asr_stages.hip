@@ -984,11 +984,9 @@ struct StageL {
   size_t w_src, w_src_bwd, theta_dst, wbuf, wbuf_bwd, act_t, mask_t, acts, masks, grp, slabs;  // workspace offsets
   size_t act_tb, xin32;  // bf16 nets: the transition's output in bf16, its input in fp32 (kept for the backward)
   bool tdirect;          // bf16 nets: the transition on the LDS kernels in bf16 (no fp32 copies)
-  bool deep;             // bf16 nets: a C = 16, 32 x 32 stage on the fused deep16 kernels (x0: its input slot,
-  size_t x0;             //   followed by the L outputs at stride P, as deep16 reads them)
-  bool img;              // bf16 nets: a 16 x 16 x 32 / 8 x 8 x 64 stage on the image-resident kernels
-  bool img32;            // fp32 nets: the same on the fp32 image-resident kernels
-  size_t dys;            //   its backward's per-layer input gradients (layers 0 .. L-2)
+  int fused;             // fused_stage_kind: the L blocks in one launch (deep16, image-resident) or, kFusedNone, per block
+  size_t x0;             //   a fused stage's input slot, followed by the L outputs at stride P
+  size_t dys;            //   image-resident: its backward's per-layer input gradients
   long wstride;          // elements of one layer's W in wbuf (E fp32, or the bf16 MFMA pack)
   long grp_stride;   // floats per block of pass-1 group rows
   long slab_stride;  // floats per block of weight-gradient slabs
@@ -1048,12 +1046,7 @@ SLayout stages_layout(const asr_stages_config* c) {
   L.act_bytes = L.bf ? 2 : 4;
   // offset 0 is a reserved null page: a buffer offset left unassigned (0) can never alias a live
   // buffer, and stages_layout_valid rejects it
-  size_t off = 256;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += align_up(bytes, 256);
-    return o;
-  };
+  WsCursor ws{256};
   long po = 0;
   L.off_c1k = po;
   po += 9L * c->Cin * c->C[0];
@@ -1079,9 +1072,7 @@ SLayout stages_layout(const asr_stages_config* c) {
     g.P = (long)c->N * H * W * g.C;
     L.Pmax = std::max(L.Pmax, g.P);
     g.ntheta = theta_count(g.C, c->param_kind, c->antisymmetric);
-    g.deep = c->dtype == ASR_BF16 && g.L > 0 && deep16_supported(H, W, g.C);
-    g.img = c->dtype == ASR_BF16 && g.L > 0 && !g.deep && stage_img_supported(H, W, g.C);
-    g.img32 = c->dtype != ASR_BF16 && g.L > 0 && stage_img32_supported(H, W, g.C);
+    g.fused = g.L > 0 ? fused_stage_kind(H, W, g.C, c->dtype) : kFusedNone;
     g.E = 9L * g.C * g.C;
     g.blk_stride = g.ntheta + g.C;
     g.mask_bytes = (long)align_up((size_t)asr_mask_bytes(c->N, H, W, g.C), 256);
@@ -1097,60 +1088,61 @@ SLayout stages_layout(const asr_stages_config* c) {
   po += c->num_classes;
   L.n_params = po;
   // workspace
-  if (!L.st[0].deep && !L.st[0].img && !L.st[0].img32)
-    L.act0 = take((size_t)c->N * c->H * c->W * c->C[0] * L.act_bytes);
+  if (L.st[0].fused == kFusedNone)
+    L.act0 = ws.take((size_t)c->N * c->H * c->W * c->C[0] * L.act_bytes);
   L.cws_bytes = 0;
   L.tws_bytes = 0;
   for (int s = 0; s < L.ns; ++s) {
     StageL& g = L.st[s];
-    g.w_src = take((size_t)g.E * 4);
-    g.theta_dst = take((size_t)g.ntheta * 2 * 4);
-    g.w_src_bwd = L.sep_bwd ? take((size_t)g.E * 4) : 0;
+    g.w_src = ws.take((size_t)g.E * 4);
+    g.theta_dst = ws.take((size_t)g.ntheta * 2 * 4);
+    g.w_src_bwd = L.sep_bwd ? ws.take((size_t)g.E * 4) : 0;
     g.wstride = L.bf ? asr_wpack_elems(g.C) : g.E;
-    g.wbuf = take((size_t)std::max(g.L, 1) * g.wstride * L.act_bytes);
-    g.wbuf_bwd = L.sep_bwd ? take((size_t)std::max(g.L, 1) * g.wstride * L.act_bytes) : 0;
+    g.wbuf = ws.take((size_t)std::max(g.L, 1) * g.wstride * L.act_bytes);
+    g.wbuf_bwd = L.sep_bwd ? ws.take((size_t)std::max(g.L, 1) * g.wstride * L.act_bytes) : 0;
     g.tdirect = L.bf && g.S && trans_lds_supported(g.Hp, g.Wp, g.Cp, g.C, g.S);
     L.any_tconv = L.any_tconv || (L.bf && g.S && !g.tdirect);
-    if (g.deep || g.img || g.img32) {  // [x0 | x1 .. xL] contiguous; the stem or the transition writes x0 in place
-      g.x0 = take((size_t)(g.L + 1) * g.P * L.act_bytes);
+    if (g.fused != kFusedNone) {  // [x0 | x1 .. xL] contiguous; the stem or the transition writes x0 in place
+      g.x0 = ws.take((size_t)(g.L + 1) * g.P * L.act_bytes);
       g.acts = g.x0 + (size_t)g.P * L.act_bytes;
       if (s == 0) L.act0 = g.x0;
     }
-    g.act_t = g.S && !g.tdirect ? (g.img32 ? g.x0 : take((size_t)g.P * 4)) : 0;  // (after x0: it may be x0)
-    g.act_tb = g.S && L.bf ? ((g.deep || g.img) && g.tdirect ? g.x0 : take((size_t)g.P * 2)) : 0;
-    g.xin32 = g.S && L.bf && !g.tdirect ? take((size_t)c->N * g.Hp * g.Wp * g.Cp * 4) : 0;
-    g.mask_t = g.S ? take((size_t)g.P) : 0;
-    if (!g.deep && !g.img && !g.img32) g.acts = take((size_t)std::max(g.L, 1) * g.P * L.act_bytes);
-    g.masks = take((size_t)std::max(g.L, 1) * g.mask_bytes);
-    g.dys = g.img || g.img32 ? take((size_t)g.L * g.P * L.act_bytes) : 0;
+    // (after x0: a fp32 image-resident stage's transition writes x0 in place)
+    g.act_t = g.S && !g.tdirect ? (g.fused == kFusedImg && !L.bf ? g.x0 : ws.take((size_t)g.P * 4)) : 0;
+    g.act_tb = g.S && L.bf ? (g.fused != kFusedNone && g.tdirect ? g.x0 : ws.take((size_t)g.P * 2)) : 0;
+    g.xin32 = g.S && L.bf && !g.tdirect ? ws.take((size_t)c->N * g.Hp * g.Wp * g.Cp * 4) : 0;
+    g.mask_t = g.S ? ws.take((size_t)g.P) : 0;
+    if (g.fused == kFusedNone) g.acts = ws.take((size_t)std::max(g.L, 1) * g.P * L.act_bytes);
+    g.masks = ws.take((size_t)std::max(g.L, 1) * g.mask_bytes);
+    g.dys = g.fused == kFusedImg ? ws.take((size_t)g.L * g.P * L.act_bytes) : 0;
     // every block keeps its slabs until the stage's one reduction launch: sized by the
     // grid the fp32 weight gradient runs at this shape, not by the 512-row maximum
     // (deep16: its own slab rows per layer)
-    g.slab_rows = g.deep ? (int)(deep16_slab_bytes(c->N, 1) / ((size_t)(g.E + g.C) * 4))
+    g.slab_rows = g.fused == kFusedDeep16 ? (int)(deep16_slab_bytes(c->N, 1) / ((size_t)(g.E + g.C) * 4))
                          : f32_block_slab_rows(c->N, g.H, g.W, g.C);
     g.grp_stride = (long)reduce_groups(g.slab_rows) * (g.E + g.C);
-    g.grp = take((size_t)std::max(g.L, 1) * g.grp_stride * 4);
+    g.grp = ws.take((size_t)std::max(g.L, 1) * g.grp_stride * 4);
     g.slab_stride = (long)g.slab_rows * (g.E + g.C);
-    g.slabs = take(g.deep ? deep16_slab_bytes(c->N, g.L) : (size_t)g.L * g.slab_stride * 4);
+    g.slabs = ws.take(g.fused == kFusedDeep16 ? deep16_slab_bytes(c->N, g.L) : (size_t)g.L * g.slab_stride * 4);
     if (g.L > 0) L.cws_bytes = std::max(L.cws_bytes, asr_conv_backward_workspace_bytes(c->N, g.H, g.W, g.C, ASR_F32));
     if (g.S) L.tws_bytes = std::max(L.tws_bytes, trans_ws_bytes(c->N, g.Hp, g.Wp, g.Cp, g.C, g.S));
   }
   const int K = c->num_classes;
-  L.probs = take((size_t)c->N * K * 4);
-  L.loss_per = take((size_t)c->N * 4);
-  L.dlogits = take((size_t)c->N * K * 4);
-  L.gap = take((size_t)c->N * Cp * 4);
-  L.dA = take((size_t)L.Pmax * 4);
-  L.dB = take((size_t)L.Pmax * 4);
-  L.cws = take(std::max<size_t>(L.cws_bytes, 256));
-  L.tws = take(std::max<size_t>(L.tws_bytes, 256));
-  L.t32a = L.any_tconv ? take((size_t)L.Pmax * 4) : 0;
-  L.t32b = L.any_tconv ? take((size_t)L.Pmax * 4) : 0;
+  L.probs = ws.take((size_t)c->N * K * 4);
+  L.loss_per = ws.take((size_t)c->N * 4);
+  L.dlogits = ws.take((size_t)c->N * K * 4);
+  L.gap = ws.take((size_t)c->N * Cp * 4);
+  L.dA = ws.take((size_t)L.Pmax * 4);
+  L.dB = ws.take((size_t)L.Pmax * 4);
+  L.cws = ws.take(std::max<size_t>(L.cws_bytes, 256));
+  L.tws = ws.take(std::max<size_t>(L.tws_bytes, 256));
+  L.t32a = L.any_tconv ? ws.take((size_t)L.Pmax * 4) : 0;
+  L.t32b = L.any_tconv ? ws.take((size_t)L.Pmax * 4) : 0;
   const long E1 = 9L * c->Cin * c->C[0];
-  L.sslabs = take((size_t)kMaxStemSlabs * (E1 + c->C[0]) * 4);
+  L.sslabs = ws.take((size_t)kMaxStemSlabs * (E1 + c->C[0]) * 4);
   L.sred_bytes = reduce_ws_bytes(kMaxStemSlabs, E1 + c->C[0]);
-  L.sred = take(L.sred_bytes);
-  L.total = off;
+  L.sred = ws.take(L.sred_bytes);
+  L.total = ws.off;
   return L;
 }
 
@@ -1163,8 +1155,8 @@ bool stages_layout_valid(const SLayout& L) {
     if (g.S && !(L.bf ? g.act_tb : g.act_t)) return false;
     if (g.S && L.bf && !g.tdirect && (!g.act_t || !g.xin32)) return false;
     if (g.L > 0 && (!g.acts || !g.masks || !g.wbuf || !g.slabs || !g.grp)) return false;
-    if ((g.deep || g.img || g.img32) && !g.x0) return false;
-    if ((g.img || g.img32) && !g.dys) return false;
+    if (g.fused != kFusedNone && !g.x0) return false;
+    if (g.fused == kFusedImg && !g.dys) return false;
   }
   return true;
 }
@@ -1227,29 +1219,14 @@ int stages_forward_impl(const asr_stages_config* c, const SLayout& L, const floa
       }
     }
     if (g.L == 0) continue;
-    if (g.img32) {  // fp32: all L blocks in one launch, a workgroup per image
+    if (g.fused != kFusedNone) {  // all L blocks in one launch
       if (x != b + g.x0)
-        ASR_TRY(hip_check(hipMemcpyAsync(b + g.x0, x, (size_t)g.P * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync"));
-      ASR_TRY(stage_img32_forward((const float*)(b + g.x0), (float*)(b + g.acts), g.P, (uint8_t*)(b + g.masks),
-                                  g.mask_bytes, (const float*)(b + g.wbuf), g.wstride, params + g.off_blk + g.ntheta,
-                                  g.blk_stride, c->h, c->N, g.H, g.W, g.C, g.L, s));
-      x = b + g.acts + (size_t)(g.L - 1) * g.P * 4;
-      continue;
-    }
-    if (g.img) {  // all L blocks in one launch, a workgroup per image
-      if (x != b + g.x0)
-        ASR_TRY(hip_check(hipMemcpyAsync(b + g.x0, x, (size_t)g.P * 2, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync"));
-      ASR_TRY(stage_img_forward(b + g.x0, b + g.acts, g.P, (uint8_t*)(b + g.masks), g.mask_bytes, b + g.wbuf, g.wstride,
-                                params + g.off_blk + g.ntheta, g.blk_stride, c->h, c->N, g.H, g.W, g.C, g.L, s));
-      x = b + g.acts + (size_t)(g.L - 1) * g.P * 2;
-      continue;
-    }
-    if (g.deep) {  // all L blocks in one launch, images resident in LDS
-      if (x != b + g.x0)
-        ASR_TRY(hip_check(hipMemcpyAsync(b + g.x0, x, (size_t)g.P * 2, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync"));
-      ASR_TRY(deep16_forward(b + g.x0, b + g.acts, g.P, (uint8_t*)(b + g.masks), g.mask_bytes, b + g.wbuf,
-                             params + g.off_blk + g.ntheta, g.blk_stride, c->h, c->N, g.L, true, s));
-      x = b + g.acts + (size_t)(g.L - 1) * g.P * 2;
+        ASR_TRY(hip_check(hipMemcpyAsync(b + g.x0, x, (size_t)g.P * L.act_bytes, hipMemcpyDeviceToDevice, s),
+                          "hipMemcpyAsync"));
+      ASR_TRY(fused_stage_forward(g.fused, wdt, b + g.x0, b + g.acts, g.P, (uint8_t*)(b + g.masks), g.mask_bytes,
+                                  b + g.wbuf, g.wstride, params + g.off_blk + g.ntheta, g.blk_stride, c->h, c->N, g.H,
+                                  g.W, g.C, g.L, true, s));
+      x = b + g.acts + (size_t)(g.L - 1) * g.P * L.act_bytes;
       continue;
     }
     for (int l = 0; l < g.L; ++l) {
@@ -1386,37 +1363,16 @@ int asr_stages_forward_backward(const asr_stages_config* cfg, const float* param
     const unsigned char* chain_in = g.S ? b + (L.bf ? g.act_tb : g.act_t) : prev_out;
     const float gam = L.sep_bwd ? 0.f : cfg->gamma;
     int nsl = 0;
-    if (g.deep) {  // all L blocks in one launch (dx resident in LDS), one slab set per layer
-      int rows = 0, in_b = 0;
-      ASR_TRY(deep16_backward(d, e, b + g.x0, g.P, (const uint8_t*)(b + g.masks), g.mask_bytes,
-                              b + (L.sep_bwd ? g.wbuf_bwd : g.wbuf), cfg->h, 2.f * gam, N, g.L,
-                              (float*)(b + g.slabs), &rows, &in_b, s));
-      if (rows != g.slab_rows) return fail(ASR_E_WORKSPACE, "asr_stages: deep16 slab rows %d != %d", rows, g.slab_rows);
-      if (in_b) std::swap(d, e);
-      ASR_TRY(reduce_slabs_to_groups((const float*)(b + g.slabs), g.L * rows, g.E + g.C, (float*)(b + g.grp), s));
-      ASR_TRY(project_layers((float*)(b + g.grp), g.grp_stride, reduce_groups(rows), g.E, g.C,
-                             (const int32_t*)(b + g.theta_dst), g.ntheta, g.L, grads + g.off_blk, g.blk_stride, s));
+    if (g.fused != kFusedNone) {  // all L blocks in one launch; x_l = x0 + l P
+      int in_e = 0;
+      ASR_TRY(fused_stage_backward("asr_stages", g.fused, cfg->dtype, d, e, &in_e, nullptr, b + g.dys, b + g.x0, g.P,
+                                   (const uint8_t*)(b + g.masks), g.mask_bytes, b + (L.sep_bwd ? g.wbuf_bwd : g.wbuf),
+                                   g.wstride, cfg->h, 2.f * gam, N, g.H, g.W, g.C, g.L, (float*)(b + g.slabs),
+                                   g.slab_stride, g.slab_rows, (float*)(b + g.grp), g.grp_stride,
+                                   (const int32_t*)(b + g.theta_dst), g.ntheta, grads + g.off_blk, g.blk_stride, s));
+      if (in_e) std::swap(d, e);
     }
-    if (g.img) {  // input gradients in one launch; then each layer's weight gradient from its stored input gradient
-      ASR_TRY(stage_img_backward(d, b + g.dys, g.P, e, (const uint8_t*)(b + g.masks), g.mask_bytes,
-                                 b + (L.sep_bwd ? g.wbuf_bwd : g.wbuf), g.wstride, cfg->h, 2.f * gam, N, g.H, g.W, g.C,
-                                 g.L, s));
-      // every layer's weight gradient in one launch: x_l = x0 + l P, its input gradient dys + l P
-      ASR_TRY(wgradb_layers(b + g.x0, g.P, b + g.dys, g.P, (const uint8_t*)(b + g.masks), g.mask_bytes, cfg->h, N, g.H,
-                            g.W, g.C, g.L, (float*)(b + g.slabs), g.slab_stride, &nsl, s));
-      if (nsl > g.slab_rows) return fail(ASR_E_WORKSPACE, "asr_stages: %d slab rows > the workspace's %d", nsl, g.slab_rows);
-      std::swap(d, e);
-    }
-    if (g.img32) {  // fp32: input gradients in one launch, every layer's weight gradient in one launch
-      ASR_TRY(stage_img32_backward((const float*)d, (float*)(b + g.dys), g.P, (float*)e, (const uint8_t*)(b + g.masks),
-                                   g.mask_bytes, (const float*)(b + (L.sep_bwd ? g.wbuf_bwd : g.wbuf)), g.wstride,
-                                   cfg->h, 2.f * gam, N, g.H, g.W, g.C, g.L, s));
-      ASR_TRY(wgrad32_layers((const float*)(b + g.x0), g.P, (const float*)(b + g.dys), g.P, (const uint8_t*)(b + g.masks),
-                             g.mask_bytes, cfg->h, N, g.H, g.W, g.C, g.L, (float*)(b + g.slabs), g.slab_stride, &nsl, s));
-      if (nsl > g.slab_rows) return fail(ASR_E_WORKSPACE, "asr_stages: %d slab rows > the workspace's %d", nsl, g.slab_rows);
-      std::swap(d, e);
-    }
-    for (int l = (g.deep || g.img || g.img32) ? -1 : g.L - 1; l >= 0; --l) {
+    for (int l = g.fused != kFusedNone ? -1 : g.L - 1; l >= 0; --l) {
       const unsigned char* x_in = l == 0 ? chain_in : b + g.acts + (size_t)(l - 1) * g.P * ab;
       const unsigned char* wl = b + (L.sep_bwd ? g.wbuf_bwd : g.wbuf) + (size_t)l * g.wstride * ab;
       const uint8_t* mk = (const uint8_t*)(b + g.masks) + (size_t)l * g.mask_bytes;
@@ -1432,10 +1388,10 @@ int asr_stages_forward_backward(const asr_stages_config* cfg, const float* param
                     g.slab_rows);
       std::swap(d, e);
     }
-    if (g.L > 0 && !g.deep)
+    if (g.L > 0 && g.fused == kFusedNone)
       ASR_TRY(reduce_slab_layers((const float*)(b + g.slabs), g.slab_stride, nsl, g.E + g.C, (float*)(b + g.grp),
                                  g.grp_stride, g.L, s));
-    if (g.L > 0 && !g.deep)
+    if (g.L > 0 && g.fused == kFusedNone)
       ASR_TRY(project_layers((float*)(b + g.grp), g.grp_stride, reduce_groups(nsl), g.E, g.C,
                              (const int32_t*)(b + g.theta_dst), g.ntheta, g.L, grads + g.off_blk, g.blk_stride, s));
     if (g.S) {

@@ -15,8 +15,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "differential_equations_resnet_amd/csrc"
-SOURCES = ["asr_theta.hip", "asr_block_mfma.hip", "asr_conv_f32.hip", "asr_stem_head.hip", "asr_api.hip",
-           "asr_dist.hip", "asr_deep16.hip", "asr_stages.hip"]
+SOURCES = ["asr_theta.hip", "asr_block_mfma.hip", "asr_conv_f32.hip", "asr_conv_kxk.hip", "asr_stem_head.hip",
+           "asr_api.hip", "asr_dist.hip", "asr_deep16.hip", "asr_stages.hip"]
 META = ["vgpr_count", "sgpr_count", "vgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size"]
 
 
@@ -28,6 +28,8 @@ def kernels(asm):
         if not name.startswith('_Z') or 's_endpgm' not in f:
             continue  # (data symbols and the metadata that follows them)
         # (a label's "; in Loop: Header=BBn_m" comment carries the function's index in its file)
+        # (the file's metadata notes follow its last kernel: kernel_metadata reads them, per kernel)
+        f = f.split('.amdgpu_metadata', 1)[0]
         body = [re.sub(r'\.LBB\d+_\d+', 'L', l.split(';', 1)[0].strip()) for l in f.split('\n')[1:]]
         # (the trailing __hip_cuid_<hash of the source file> symbol is not code)
         out[name] = [l for l in body if l and not l.startswith(('.', '__hip_cuid_'))]
