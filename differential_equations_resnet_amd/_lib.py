@@ -29,7 +29,7 @@ ASR_BF16 = 1
 ASR_PARAM_3BY3 = 0
 ASR_PARAM_GENERAL = 1
 ASR_PARAM_REGULAR = 2
-ABI_VERSION = 9
+ABI_VERSION = 10
 ASR_MODE_EULER = 0
 ASR_MODE_CONV = 1
 ASR_INTEGRATOR_EULER = 0
@@ -62,6 +62,7 @@ class NetConfig(ct.Structure):
         ("num_classes", ct.c_int), ("h", ct.c_float), ("gamma", ct.c_float), ("subtract_mean", ct.c_float),
         ("divide_by_stddev", ct.c_float), ("use_norm", ct.c_int), ("dtype", ct.c_int), ("input_u8", ct.c_int),
         ("param_kind", ct.c_int), ("antisymmetric", ct.c_int), ("integrator", ct.c_int), ("variant", ct.c_int),
+        ("kernel_size", ct.c_int), ("conv1_kernel_size", ct.c_int),  # 0 means 3 (ABI 10)
     ]
 
 

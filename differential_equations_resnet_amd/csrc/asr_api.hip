@@ -65,9 +65,9 @@ struct StemWs {
   size_t dz, slabs, red, total;
 };
 
-static StemWs stem_ws_layout(long P, int Cin, int C) {
+static StemWs stem_ws_layout(long P, int Cin, int C, int K = 3) {
   StemWs w{};
-  const long ES1 = 9L * Cin * C + C;
+  const long ES1 = (long)K * K * Cin * C + C;
   WsCursor c;
   w.dz = c.take((size_t)P * 4);
   w.slabs = c.take((size_t)kMaxBlockSlabs * ES1 * 4);
@@ -295,7 +295,26 @@ struct NetLayout {
   size_t grow;        // stacked Euler backward: dL/dx_L as one bf16 row per image (the GAP gradient) [N][C]
   BwdWs bw;           // inside bwdws: one block's backward workspace (asr_conv_backward's layout) ...
   StemWs stem;        // ... and, after the blocks, the stem's
+  int k1, kb;         // conv1's and the blocks' kernel size (3, 5 or 7)
+  bool stem_kxk;      // k1 != 3 on a shape of the bf16 matrix-core k x k stem (stem_kxk_supported)
+  bool kxk;           // kb != 3: one launch per block on the k x k kernels, no stack
+  int kxk_rows;       // ... whose weight gradient writes this many slab rows per block
 };
+
+// asr_net_config's kernel sizes: 0 means 3
+static int net_k1(const asr_net_config* c) { return c->conv1_kernel_size ? c->conv1_kernel_size : 3; }
+static int net_kb(const asr_net_config* c) { return c->kernel_size ? c->kernel_size : 3; }
+
+static const char kNetKernelSizes[] =
+    "kernel_size and conv1_kernel_size in {0 (= 3), 3, 5, 7}; kernel_size 5 / 7: ASR_PARAM_GENERAL or "
+    "ASR_PARAM_REGULAR blocks, Euler integrator, float32 at any shape, bfloat16 at C in {16, 32, 64} and "
+    "W in {8, 16, 32}; kernel_size 3 in bfloat16: C in {16, 32, 64} and W == 32";
+
+static int check_net_kernel_size(const char* field, int k) {
+  if (k == 3 || k == 5 || k == 7) return ASR_OK;
+  return fail((k < 1 || !(k & 1)) ? ASR_E_ARG : ASR_E_UNSUPPORTED, "%s %d: the network takes %s", field, k,
+              kNetKernelSizes);
+}
 
 static int net_check(const asr_net_config* c) {
   if (!c) return fail(ASR_E_ARG, "null config");
@@ -314,6 +333,20 @@ static int net_check(const asr_net_config* c) {
                     ASR_VARIANT_PER_BLOCK_BWD | ASR_VARIANT_INFERENCE | ASR_VARIANT_TIMED | ASR_VARIANT_FULL_DXL |
                     ASR_VARIANT_FULL_SLABS | ASR_VARIANT_W_BF16))
     return fail(ASR_E_ARG, "bad variant bits 0x%x", c->variant);
+  const int kb = net_kb(c);
+  ASR_TRY(check_net_kernel_size("conv1_kernel_size", net_k1(c)));
+  ASR_TRY(check_net_kernel_size("kernel_size", kb));
+  if (kb != 3) {
+    if (c->param_kind == ASR_PARAM_3BY3)
+      return fail(ASR_E_ARG, "the 3by3 parametrisation has kernel_size 3 (kernel_size=%d): the network takes %s", kb,
+                  kNetKernelSizes);
+    if (c->integrator == ASR_INTEGRATOR_RK2)
+      return fail(ASR_E_UNSUPPORTED, "RK2 blocks with kernel_size %d: the network takes %s", kb, kNetKernelSizes);
+    if (c->dtype == ASR_BF16 && !convk_bf16_supported(kb, c->W, c->C))
+      return fail(ASR_E_UNSUPPORTED, "bf16 network with kernel_size %d at C=%d W=%d: the network takes %s", kb, c->C,
+                  c->W, kNetKernelSizes);
+    return ASR_OK;
+  }
   if (c->dtype == ASR_BF16 && !mfma_supported(c->C, c->W))
     return fail(ASR_E_UNSUPPORTED, "bf16 network needs C in {16,32,64} and W == 32 (C=%d W=%d)", c->C, c->W);
   return ASR_OK;
@@ -322,27 +355,31 @@ static int net_check(const asr_net_config* c) {
 static NetLayout net_layout(const asr_net_config* c) {
   NetLayout L{};
   const int C = c->C, K = c->num_classes;
-  L.ntheta = theta_count(C, c->param_kind, c->antisymmetric);
+  L.k1 = net_k1(c);
+  L.kb = net_kb(c);
+  L.kxk = L.kb != 3;
+  L.ntheta = theta_count_k(C, L.kb, c->param_kind, c->antisymmetric);
   L.sep_bwd = param_is_antisymmetric(c->param_kind, c->antisymmetric) == 0;
   L.rk2 = c->integrator == ASR_INTEGRATOR_RK2;
   L.stages = L.rk2 ? 2 : 1;
   L.P = (long)c->N * c->H * c->W * C;
-  L.E = 9L * C * C;
+  L.E = (long)L.kb * L.kb * C * C;
   L.act_bytes = c->dtype == ASR_BF16 ? 2 : 4;
-  L.wstride = c->dtype == ASR_BF16 ? (long)(C / 16) * ((9 * C + 31) / 32) * 512 : L.E;
+  L.wstride = c->dtype == ASR_BF16 ? (long)(C / 16) * ((L.kb * L.kb * C + 31) / 32) * 512 : L.E;
   L.off_c1k = 0;
-  L.off_c1b = 9L * c->Cin * C;
+  L.off_c1b = (long)L.k1 * L.k1 * c->Cin * C;
   L.off_blk = L.off_c1b + C;
   L.blk_stride = L.ntheta + C;
   L.off_fck = L.off_blk + (long)c->L * L.blk_stride;
   L.off_fcb = L.off_fck + (long)C * K;
   L.nparams = L.off_fcb + K;
   L.mask_bytes = asr_mask_bytes(c->N, c->H, c->W, C);
-  L.fast_stem = stem_supported(c->Cin, c->H, c->W, C);
+  L.fast_stem = L.k1 == 3 && stem_supported(c->Cin, c->H, c->W, C);
+  L.stem_kxk = c->dtype == ASR_BF16 && L.k1 != 3 && stem_kxk_supported(L.k1, c->Cin, c->W, C);
   L.inference = (c->variant & ASR_VARIANT_INFERENCE) != 0;
   const bool tr = !L.inference;  // training buffers
-  L.deep = c->dtype == ASR_BF16 && !L.rk2 && deep16_supported(c->H, c->W, C);
-  L.stack_bwd = tr && c->dtype == ASR_BF16 && block_stack_bwd_supported(c->N, c->H, c->W, C);
+  L.deep = !L.kxk && c->dtype == ASR_BF16 && !L.rk2 && deep16_supported(c->H, c->W, C);
+  L.stack_bwd = !L.kxk && tr && c->dtype == ASR_BF16 && block_stack_bwd_supported(c->N, c->H, c->W, C);
   L.stack_grid = L.stack_bwd ? block_stack_bwd_grid(c->N) : 0;
   L.stack_pair = L.stack_bwd && !L.sep_bwd;
   WsCursor ws;
@@ -362,19 +399,21 @@ static NetLayout net_layout(const asr_net_config* c) {
   // per-block backward workspace (asr_conv_backward layout), reused by the stem.
   // fp32 keeps every block's slabs in slabs_all, sized by the grid its weight
   // gradient runs (not the 512-row maximum): no slab rows here, no slabs2
+  // k x k blocks: one slab set in the backward workspace, reduced into the block's group sums right after its launch
   const bool f32 = c->dtype == ASR_F32;
-  L.f32_rows = f32 ? f32_block_slab_rows(c->N, c->H, c->W, C) : 0;
-  L.bw = bwd_ws_layout(c->N, c->H, c->W, C, c->dtype, L.stages, 3, f32 ? 0 : -1);
-  L.stem = stem_ws_layout(L.P, c->Cin, C);
+  L.kxk_rows = !L.kxk ? 0 : f32 ? wgrad_f32_chunks(c->N, c->H) : wgradk_bf16_slab_rows(L.kb, c->N, c->H, c->W, C);
+  L.f32_rows = f32 && !L.kxk ? f32_block_slab_rows(c->N, c->H, c->W, C) : 0;
+  L.bw = bwd_ws_layout(c->N, c->H, c->W, C, c->dtype, L.stages, L.kb, L.kxk ? L.kxk_rows : f32 ? 0 : -1);
+  L.stem = stem_ws_layout(L.P, c->Cin, C, L.k1);
   L.bwdws = ws.take(tr ? std::max(L.bw.total, L.stem.total) : 0);
   // odd Euler blocks' slabs (even ones use the backward workspace's): a
   // block's slabs stay readable while the next block's kernel reduces them
-  L.slabs2 = ws.take(tr && !f32 ? (size_t)L.stages * kMaxBlockSlabs * (L.E + C) * 4 : 0);  // every other block's slabs
-  const int rows = f32 ? L.stages * L.f32_rows : L.stages * kMaxBlockSlabs;
+  L.slabs2 = ws.take(tr && !f32 && !L.kxk ? (size_t)L.stages * kMaxBlockSlabs * (L.E + C) * 4 : 0);  // every other block's slabs
+  const int rows = L.kxk ? L.kxk_rows : f32 ? L.stages * L.f32_rows : L.stages * kMaxBlockSlabs;
   L.grp_stride = (long)reduce_groups(rows) * (L.E + C);
   L.grp = ws.take(tr ? (size_t)c->L * L.grp_stride * 4 : 0);
   L.slab_stride = (long)rows * (L.E + C);
-  L.slabs_all = ws.take(tr && f32 ? (size_t)c->L * L.slab_stride * 4 : 0);
+  L.slabs_all = ws.take(tr && f32 && !L.kxk ? (size_t)c->L * L.slab_stride * 4 : 0);
   L.deep_slabs = ws.take(L.deep && tr ? deep16_slab_bytes(c->N, c->L) : 0);
   L.theta_dst_tm = ws.take(L.stack_bwd ? (size_t)L.ntheta * 2 * 4 : 0);
   L.theta_dst_pr = ws.take(L.stack_pair ? (size_t)L.ntheta * 2 * 4 : 0);
@@ -435,6 +474,23 @@ static unsigned char* net_xL(const asr_net_config* c, const NetLayout& L, unsign
   return ws + L.acts + (size_t)(c->L & 1) * a;
 }
 
+// the normalised input (v - mean) * inv_std as fp32, at L.x0: the generic stem arm's operand
+static int net_normalize(const asr_net_config* c, const NetLayout& L, const void* images, unsigned char* ws,
+                         hipStream_t s) {
+  const float inv_std = c->use_norm ? 1.f / c->divide_by_stddev : 1.f;
+  const long nin = (long)c->N * c->H * c->W * c->Cin;
+  float* x0 = (float*)(ws + L.x0);
+  const unsigned gn = (unsigned)std::min<long>((nin + 255) / 256, 4096);
+  if (c->input_u8)
+    hipLaunchKernelGGL(k_normalize<uint8_t>, dim3(gn), dim3(256), 0, s, (const uint8_t*)images, nin, c->subtract_mean,
+                       inv_std, c->use_norm, x0);
+  else
+    hipLaunchKernelGGL(k_normalize<float>, dim3(gn), dim3(256), 0, s, (const float*)images, nin, c->subtract_mean,
+                       inv_std, c->use_norm, x0);
+  ASR_LAUNCH_CHECK("k_normalize");
+  return ASR_OK;
+}
+
 static int net_forward_impl(const asr_net_config* c, const NetLayout& L, const float* params, const void* images,
                             bool training, unsigned char* ws, hipStream_t s, unsigned char** xL_out = nullptr) {
   const int C = c->C, N = c->N, H = c->H, W = c->W;
@@ -444,7 +500,21 @@ static int net_forward_impl(const asr_net_config* c, const NetLayout& L, const f
   // 1. materialise W for all L blocks (one launch)
   //    (bf16: balanced rounding of the antisymmetric pairs, k_theta_to_w_pack_bal; ASR_VARIANT_W_BF16: to nearest)
   const bool bal = !(c->variant & ASR_VARIANT_W_BF16);
-  if (bf)
+  if (L.kxk) {  // k x k blocks: the single-layer ABI's packs (bf16 rounded to nearest), all L layers per launch
+    const float* th = params + L.off_blk;
+    const int32_t* src = (const int32_t*)(ws + L.w_src);
+    const int32_t* src_bwd = (const int32_t*)(ws + L.w_src_bwd);
+    if (bf) {
+      ASR_TRY(asr_theta_to_w_k_bf16(th, L.blk_stride, c->L, C, L.kb, src, c->gamma, ws + L.wbuf, L.wstride, s));
+      if (training && L.sep_bwd)
+        ASR_TRY(asr_theta_to_w_k_bf16(th, L.blk_stride, c->L, C, L.kb, src_bwd, 0.f, ws + L.wbuf_bwd, L.wstride, s));
+    } else {
+      ASR_TRY(asr_theta_to_w_k(th, L.blk_stride, c->L, C, L.kb, src, c->gamma, (float*)(ws + L.wbuf), L.wstride, s));
+      if (training && L.sep_bwd)
+        ASR_TRY(asr_theta_to_w_k(th, L.blk_stride, c->L, C, L.kb, src_bwd, 0.f, (float*)(ws + L.wbuf_bwd), L.wstride,
+                                 s));
+    }
+  } else if (bf)
     ASR_TRY(theta_to_w_bf16(params + L.off_blk, L.blk_stride, c->L, C, (const int32_t*)(ws + L.w_src), c->gamma,
                             ws + L.wbuf, L.wstride, bal, s,
                             c->param_kind != ASR_PARAM_REGULAR ? (const int32_t*)(ws + L.theta_dst) : nullptr,
@@ -452,7 +522,7 @@ static int net_forward_impl(const asr_net_config* c, const NetLayout& L, const f
   else
     ASR_TRY(asr_theta_to_w(params + L.off_blk, L.blk_stride, c->L, C, (const int32_t*)(ws + L.w_src), c->gamma,
                            ws + L.wbuf, L.wstride, c->dtype, s));
-  if (training && L.sep_bwd) {  // (the transposed map pairs the same entries: W_bwd = -W^T after the rounding too)
+  if (training && L.sep_bwd && !L.kxk) {  // (the transposed map pairs the same entries: W_bwd = -W^T after the rounding too)
     if (bf)
       ASR_TRY(theta_to_w_bf16(params + L.off_blk, L.blk_stride, c->L, C, (const int32_t*)(ws + L.w_src_bwd), 0.f,
                               ws + L.wbuf_bwd, L.wstride, bal, s));
@@ -470,22 +540,17 @@ static int net_forward_impl(const asr_net_config* c, const NetLayout& L, const f
   if (L.fast_stem && bf && stem_fwd_mfma_supported(c->Cin, H, W, C) && !(c->variant & ASR_VARIANT_STEM_FWD_VALU)) {
     ASR_TRY(stem_fwd_mfma(images, c->input_u8, params + L.off_c1k, params + L.off_c1b, N, H, W, c->Cin, C,
                           c->subtract_mean, inv_std, c->use_norm, act(0), s));
+  } else if (L.stem_kxk && !(c->variant & ASR_VARIANT_STEM_FWD_VALU)) {
+    ASR_TRY(stem_fwd_kxk(L.k1, images, c->input_u8, params + L.off_c1k, params + L.off_c1b, N, H, W, c->Cin, C,
+                         c->subtract_mean, inv_std, c->use_norm, act(0), s));
   } else if (L.fast_stem) {
     ASR_TRY(stem_forward(images, c->input_u8, params + L.off_c1k, params + L.off_c1b, N, H, W, c->Cin, C,
                          c->subtract_mean, inv_std, c->use_norm, act(0), bf ? 1 : 0, s));
   } else {
-    const long nin = (long)N * H * W * c->Cin;
     float* x0 = (float*)(ws + L.x0);
-    const unsigned gn = (unsigned)std::min<long>((nin + 255) / 256, 4096);
-    if (c->input_u8)
-      hipLaunchKernelGGL(k_normalize<uint8_t>, dim3(gn), dim3(256), 0, s, (const uint8_t*)images, nin,
-                         c->subtract_mean, inv_std, c->use_norm, x0);
-    else
-      hipLaunchKernelGGL(k_normalize<float>, dim3(gn), dim3(256), 0, s, (const float*)images, nin,
-                         c->subtract_mean, inv_std, c->use_norm, x0);
-    ASR_LAUNCH_CHECK("k_normalize");
+    ASR_TRY(net_normalize(c, L, images, ws, s));
     ASR_TRY(conv_f32(F_RELU, x0, act(0), nullptr, params + L.off_c1k, params + L.off_c1b, 1.f, 0.f, nullptr, N, H,
-                     W, c->Cin, C, bf ? 1 : 0, s));
+                     W, c->Cin, C, bf ? 1 : 0, s, nullptr, L.k1));
   }
   // 3. L Euler blocks (tfkeras_resnets.py:579-582 -> :28-94), or RK2 blocks
   ASR_TRY(timed_event(c, 0, s));
@@ -503,7 +568,7 @@ static int net_forward_impl(const asr_net_config* c, const NetLayout& L, const f
                                      L.blk_stride, c->h, N, H, W, C, c->L, s));
     return timed_event(c, 1, s);
   }
-  if (bf && !L.rk2 && (training || L.inference) && block_stack_fwd_supported(N, H, W, C) &&
+  if (bf && !L.rk2 && !L.kxk && (training || L.inference) && block_stack_fwd_supported(N, H, W, C) &&
       !(c->variant & ASR_VARIANT_PER_BLOCK_FWD)) {
     // C=64: all L blocks in one launch (whole images per workgroup); inference
     // ping-pongs x_l between slots 1 and 2 with no relu masks
@@ -527,6 +592,11 @@ static int net_forward_impl(const asr_net_config* c, const NetLayout& L, const f
       unsigned char* xm = ws + L.xmids + (training ? (size_t)l * L.P * L.act_bytes : 0);
       uint8_t* mask2 = training ? mask + (size_t)c->L * L.mask_bytes : nullptr;
       ASR_TRY(rk2_forward_impl(act(l), xm, act(l + 1), mask, mask2, wl, bias, c->h, N, H, W, C, c->dtype, s));
+    } else if (L.kxk && bf) {
+      ASR_TRY(convk_bf16(F_EULER, L.kb, act(l), act(l + 1), mask, wl, bias, c->h, 0.f, nullptr, N, H, W, C, s));
+    } else if (L.kxk) {
+      ASR_TRY(conv_f32_k(F_EULER, L.kb, act(l), act(l + 1), mask, (const float*)wl, bias, c->h, 0.f, nullptr, N, H, W,
+                         C, s, nullptr));
     } else if (bf) {
       ASR_TRY(block_fwd_mfma(0, act(l), nullptr, act(l + 1), mask, wl, bias, c->h, N, H, W, C, s));
     } else {
@@ -1046,11 +1116,11 @@ int asr_net_prepare(const asr_net_config* cfg, void* ws, size_t ws_bytes) {
   if (!ws || ws_bytes < L.total) return fail(ASR_E_WORKSPACE, "asr_net_prepare: workspace too small");
   ASR_TRY(check_ws_device(ws, "asr_net_prepare"));
   std::vector<int32_t> w_src((size_t)L.E), theta_dst((size_t)L.ntheta * 2);
-  ASR_TRY(param_map(cfg->C, cfg->param_kind, cfg->antisymmetric, w_src.data(), theta_dst.data()));
+  ASR_TRY(param_map_k(cfg->C, L.kb, cfg->param_kind, cfg->antisymmetric, w_src.data(), theta_dst.data()));
   unsigned char* b = (unsigned char*)ws;
   if (L.sep_bwd && !L.inference) {
     std::vector<int32_t> w_bwd((size_t)L.E);
-    ASR_TRY(param_map_transpose(cfg->C, w_src.data(), w_bwd.data()));
+    ASR_TRY(param_map_transpose_k(cfg->C, L.kb, w_src.data(), w_bwd.data()));
     ASR_TRY(hip_check(hipMemcpy(b + L.w_src_bwd, w_bwd.data(), w_bwd.size() * 4, hipMemcpyHostToDevice), "hipMemcpy"));
   }
   ASR_TRY(hip_check(hipMemcpy(b + L.w_src, w_src.data(), w_src.size() * 4, hipMemcpyHostToDevice), "hipMemcpy"));
@@ -1183,7 +1253,7 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
     float* slabs = (float*)(b + L.stack_slabs);
     float* grp = (float*)(b + L.grp);
     // (RK2: the first block's first stage has the extra term, so the stem's relu' runs separately)
-    const int ro0 = L.fast_stem && !stem_v1 && !L.rk2;
+    const int ro0 = (L.fast_stem || L.stem_kxk) && !stem_v1 && !L.rk2;
     int lfold = cfg->L;
     const uint8_t* m1 = (const uint8_t*)(b + L.masks);
     ASR_TRY(block_stack_bwd_mfma(dcur, dnext, act(0), L.P, m1, L.mask_bytes, b + (L.sep_bwd ? L.wbuf_bwd : L.wbuf),
@@ -1204,7 +1274,31 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
                            grads + L.off_blk, L.blk_stride, s));
     ASR_TRY(timed_event(cfg, 4, s));
   }
-  for (int l = (L.deep || stacked) ? -1 : cfg->L - 1; l >= 0; --l) {
+  if (L.kxk) {  // k x k blocks: one dgrad and one weight-gradient launch per block, pass 1 of its slabs right behind
+    float* slabs_k = (float*)(b + L.bwdws + L.bw.slabs);
+    float* dz_k = (float*)(b + L.bwdws + L.bw.dz);
+    for (int l = cfg->L - 1; l >= 0; --l) {
+      const unsigned char* wl = b + (L.sep_bwd ? L.wbuf_bwd : L.wbuf) + (size_t)l * L.wstride * L.act_bytes;
+      const uint8_t* mask = (const uint8_t*)(b + L.masks) + (size_t)l * L.mask_bytes;
+      const float two_gamma = L.sep_bwd ? 0.f : 2.f * cfg->gamma;
+      int nsl = 0;
+      if (bf) {
+        ASR_TRY(convk_bf16(B_EULER, L.kb, dcur, dnext, nullptr, wl, nullptr, cfg->h, two_gamma, mask, N, H, W, C, s));
+        ASR_TRY(wgradk_bf16(L.kb, act(l), dcur, mask, cfg->h, N, H, W, C, slabs_k, &nsl, s));
+      } else {
+        ASR_TRY(make_dz(F_EULER, dcur, mask, nullptr, cfg->h, N, H, W, C, 0, dz_k, s));
+        ASR_TRY(conv_f32_k(B_EULER, L.kb, dz_k, dnext, nullptr, (const float*)wl, nullptr, cfg->h, two_gamma,
+                           (const float*)dcur, N, H, W, C, s, nullptr));
+        ASR_TRY(wgrad_f32(act(l), 0, dz_k, N, H, W, C, C, slabs_k, &nsl, s, L.kb));
+      }
+      if (nsl < 1 || nsl > L.kxk_rows)  // (the device differs from the one the workspace was sized on)
+        return fail(ASR_E_WORKSPACE, "k x k block %d wrote %d slab rows, the workspace holds %d", l, nsl, L.kxk_rows);
+      ASR_TRY(reduce_slabs_to_groups(slabs_k, nsl, L.E + C, (float*)(b + L.grp) + (size_t)l * L.grp_stride, s));
+      nsl_blk = nsl;
+      std::swap(dcur, dnext);
+    }
+  }
+  for (int l = (L.deep || stacked || L.kxk) ? -1 : cfg->L - 1; l >= 0; --l) {
     const unsigned char* wl = b + (L.sep_bwd ? L.wbuf_bwd : L.wbuf) + (size_t)l * L.wstride * L.act_bytes;
     const uint8_t* mask = (const uint8_t*)(b + L.masks) + (size_t)l * L.mask_bytes;
     const float gam = L.sep_bwd ? 0.f : cfg->gamma;
@@ -1225,7 +1319,7 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
     } else {
       ASR_TRY(block_backward(ASR_MODE_EULER, dcur, act(l), mask, wl, cfg->h, gam, N, H, W, C, cfg->dtype, dnext, true,
                              nullptr, false, slabs_l, (float*)(b + L.bwdws + L.bw.dz), &nsl, s,
-                             l == 0 && L.fast_stem && bf && !stem_v1, l == 0 ? &dz1_fused : nullptr,
+                             l == 0 && (L.fast_stem || L.stem_kxk) && bf && !stem_v1, l == 0 ? &dz1_fused : nullptr,
                              fold_on ? pend_slabs : nullptr, fold_on ? pend_P : 0, pend_grp, &folded));
     }
     nsl_blk = nsl;
@@ -1242,7 +1336,7 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
     pend_grp = grp_l;
   }
   if (pend_P > 0) ASR_TRY(reduce_slabs_to_groups(pend_slabs, pend_P, L.E + C, pend_grp, s));
-  if (!bf && !L.deep && !stacked && nsl_blk > 0)  // (every block of a network has the same slab count)
+  if (!bf && !L.deep && !stacked && !L.kxk && nsl_blk > 0)  // (every block of a network has the same slab count)
     ASR_TRY(reduce_slab_layers((const float*)(b + L.slabs_all), L.slab_stride, nsl_blk, L.E + C,
                                (float*)(b + L.grp), L.grp_stride, cfg->L, s));
   // pass 2 of every block's weight-gradient reduction + projection onto theta, one launch
@@ -1253,7 +1347,7 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
     ASR_TRY(timed_event(cfg, 4, s));
   }
   // stem: dz1 = dx1 * [x1 > 0]; conv1 weight/bias gradient from the normalised input
-  const long E1 = 9L * cfg->Cin * C;
+  const long E1 = (long)L.k1 * L.k1 * cfg->Cin * C;
   float* dz = (float*)(b + L.bwdws + L.stem.dz);
   float* slabs = (float*)(b + L.bwdws + L.stem.slabs);
   float* red = (float*)(b + L.bwdws + L.stem.red);
@@ -1263,15 +1357,21 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
     ASR_TRY(relu_grad_bf16(dcur, act(0), L.P, s));
     dz1_fused = 1;
   }
-  if (L.fast_stem && dz1_fused && stem_wgrad_mfma_supported(cfg->Cin, H, W, C)) {
+  if (L.stem_kxk && !stem_v1) {  // the k x k conv1 on the matrix cores, from dz1 in bf16
+    if (!dz1_fused) ASR_TRY(relu_grad_bf16(dcur, act(0), L.P, s));
+    ASR_TRY(stem_wgrad_kxk(L.k1, images, cfg->input_u8, dcur, N, H, W, cfg->Cin, C, cfg->subtract_mean, inv_std,
+                           cfg->use_norm, slabs, &nsl, s));
+  } else if (L.fast_stem && dz1_fused && stem_wgrad_mfma_supported(cfg->Cin, H, W, C)) {
     ASR_TRY(stem_wgrad_mfma(images, cfg->input_u8, dcur, N, H, W, cfg->Cin, C, cfg->subtract_mean, inv_std,
                             cfg->use_norm, slabs, &nsl, s));
   } else if (L.fast_stem) {  // (masking an already-masked dz1 again is exact)
     ASR_TRY(stem_wgrad(images, cfg->input_u8, dcur, act(0), bf, N, H, W, cfg->Cin, C, cfg->subtract_mean, inv_std,
                        cfg->use_norm, slabs, &nsl, s));
   } else {
+    // (the forward left x0 there unless the matrix-core k x k stem ran it)
+    if (L.stem_kxk && !(cfg->variant & ASR_VARIANT_STEM_FWD_VALU)) ASR_TRY(net_normalize(cfg, L, images, b, s));
     ASR_TRY(make_dz(F_RELU, dcur, nullptr, act(0), 1.f, N, H, W, C, bf ? 1 : 0, dz, s));
-    ASR_TRY(wgrad_f32(b + L.x0, 0, dz, N, H, W, cfg->Cin, C, slabs, &nsl, s));
+    ASR_TRY(wgrad_f32(b + L.x0, 0, dz, N, H, W, cfg->Cin, C, slabs, &nsl, s, L.k1));
   }
   ASR_TRY(reduce_and_project(slabs, nsl, E1, C, nullptr, 0, nullptr, grads + L.off_c1b, grads + L.off_c1k, red, s));
   return ASR_OK;

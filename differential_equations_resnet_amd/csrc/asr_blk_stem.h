@@ -5,7 +5,9 @@
 // workgroup, the image staged in LDS as v - mean:
 //   k_stem_fwd_mfma    one k-step (27 taps x channels padded to 32), W1 as bf16 hi + lo;
 //   k_stem_wgrad_mfma  K = pixels, dz1 rows by LDS-DMA in 8-row bands, one
-//                      [dW1 | db1] slab per workgroup.
+//                      [dW1 | db1] slab per workgroup;
+//   k_stem_fwd_kxk, k_stem_wgrad_kxk  the 5 x 5 and 7 x 7 conv1 (C in {16, 32, 64}, W in {8, 16, 32}, any
+//                      H), row bands instead of whole images: below the 3 x 3 kernels.
 #pragma once
 #include <type_traits>
 
@@ -221,6 +223,223 @@ __global__ __launch_bounds__(256) void k_stem_fwd_mfma(const Tin* __restrict__ i
       }
     }
   }
+}
+
+// ===========================================================================
+// The K x K stem, K = 5 or 7 (conv1 of get_single_block_resnet_build_function(kernel_size = K),
+// models/tfkeras_resnets.py:563-572), for the bf16 networks: CIN = 3, C in {16, 32, 64}, W in {8, 16, 32},
+// any H >= 1.  The numerical contract of the 3 x 3 kernels above: the image staged in LDS as fp32 v - mean with
+// a zero halo of K/2 (bf16-exact for u8 input with a half-integer mean), inv_std * W1 as bf16 hi + lo, fp32
+// accumulation, bias and relu.  Both kernels are 256 threads and walk (image, row band) items; a band is
+// staged with its K - 1 halo rows, so H is free and no im2col is kept (at K = 7 a 32 x 32 image's would be
+// 350 KB): the patch operand is gathered from the staged image, 8 values per lane and k-step.
+// ===========================================================================
+template <int W_, int K>
+struct StemK {
+  static constexpr int W = W_, CIN = 3, KC = K * K * CIN, TW = W + K - 1;
+  static constexpr int KS = (KC + 31) / 32;      // forward k-steps: 3 (75 -> 96) at K = 5, 5 (147 -> 160) at K = 7
+  static constexpr int BRF = 512 / W;            // forward band: 512 pixels = 32 tiles of 16, 8 a wave
+  static constexpr int BRW = 256 / W;            // weight-gradient band: 256 pixels = 8 chunks of 32
+  static constexpr int MT = (KC + 1 + 15) / 16;  // weight-gradient m-tiles (kappa and the ones row): 5 / 10
+  static constexpr int MTW = (MT + 3) / 4;       // ... of one wave (tiles wave, wave + 4, ...)
+};
+
+// band rows y0 - K/2 .. of image n -> ft [ROWS][TW][3] (fp32 v - mean, zeros outside the image)
+template <int W, int K, int ROWS, typename Tin>
+__device__ __forceinline__ void stemk_stage(const Tin* __restrict__ img, int n, int y0, int H, float mean,
+                                            float* __restrict__ ft, int tid) {
+  constexpr int CIN = 3, TW = W + K - 1, R = K / 2;
+  for (int i = tid; i < ROWS * TW * CIN; i += 256) {
+    const int ci = i % CIN, c = (i / CIN) % TW, r = i / (CIN * TW);
+    const int gy = y0 + r - R, gx = c - R;
+    float v = 0.f;
+    if ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W)
+      v = (float)img[(((long)n * H + gy) * W + gx) * CIN + ci] - mean;
+    ft[i] = v;
+  }
+}
+
+// Forward: x1 = relu(conv_KxK((v - mean) * inv_std, W1) + b1), bf16 NHWC.  M = o, reduction kappa = tap * 3 + ci
+// in KS k-steps, N = 16 pixels (pixel 16 tile + lx of the band: a tile spans two rows at W = 8).  The A
+// fragments (hi + lo of every o-tile and k-step: 160 VGPRs at C = 64, K = 7) stay in registers: the 4 waves of
+// a workgroup run one per SIMD.  Two MFMAs per o-tile and k-step; the epilogue of k_stem_fwd_mfma.
+template <int C, int W, int K, typename Tin>
+__global__ __launch_bounds__(256) void k_stem_fwd_kxk(const Tin* __restrict__ img, const float* __restrict__ w1,
+                                                      const float* __restrict__ b1, int N, int H, float mean,
+                                                      float inv_std, bf16* __restrict__ out) {
+  using G = StemK<W, K>;
+  constexpr int CIN = 3, TW = G::TW, KC = G::KC, KS = G::KS, MT = C / 16, BR = G::BRF, ROWS = BR + K - 1;
+  __shared__ float ft[ROWS * TW * CIN];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, lx = lane & 15;
+  bf16x8 Ah[MT][KS], Al[MT][KS];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int kap = 32 * ks + 8 * g + j;
+        const float wv = kap < KC ? w1[kap * C + 16 * mt + lx] * inv_std : 0.f;
+        const bf16 hi = (bf16)wv;
+        Ah[mt][ks][j] = hi;
+        Al[mt][ks][j] = (bf16)(wv - (float)hi);
+      }
+  float bz[MT][4];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bz[mt][e] = b1 ? b1[16 * mt + 4 * g + e] : 0.f;
+  int koff[KS][8];  // tap (ky, kx), channel ci of kappa -> offset in ft from the pixel's own (row, col)
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int kap = min(32 * ks + 8 * g + j, KC - 1), tap = kap / CIN, ci = kap % CIN;
+      koff[ks][j] = ((tap / K) * TW + tap % K) * CIN + ci;
+    }
+  const int nb = (H + BR - 1) / BR;
+  const long items = (long)N * nb;
+  for (long item = blockIdx.x; item < items; item += gridDim.x) {
+    const int n = (int)(item / nb), y0 = (int)(item % nb) * BR;
+    __syncthreads();  // the previous band fully read
+    stemk_stage<W, K, ROWS>(img, n, y0, H, mean, ft, tid);
+    __syncthreads();
+    const int rows = min(BR, H - y0), ntiles = (rows * W + 15) / 16;
+    for (int pt = wave; pt < ntiles; pt += 4) {
+      const int p = 16 * pt + lx, yl = p / W, x = p % W;  // (yl <= BR - 1: the staged rows cover its patch)
+      const float* pb = ft + (yl * TW + x) * CIN;
+      bf16x8 B[KS];
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) B[ks][j] = (bf16)((32 * ks + 8 * g + j < KC) ? pb[koff[ks][j]] : 0.f);
+      f32x4 acc[MT];
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        acc[mt] = f32x4{bz[mt][0], bz[mt][1], bz[mt][2], bz[mt][3]};
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah[mt][ks], B[ks], acc[mt], 0, 0, 0);
+          acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Al[mt][ks], B[ks], acc[mt], 0, 0, 0);
+        }
+      }
+      // lane (g, lx): channels 16 mt + 4g + e of pixel p
+      u32x2 ov[MT];
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        bf16x4 o4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o4[e] = (bf16)fmaxf(acc[mt][e], 0.f);
+        ov[mt] = *(const u32x2*)&o4;
+      }
+      const bool live = y0 + yl < H;  // (a partial last tile: pixels past the band's rows)
+      bf16* orow = out + (((long)n * H + y0 + yl) * W + x) * C;
+      if constexpr (MT == 1) {
+        if (live) *(u32x2*)(orow + 4 * g) = ov[0];
+      } else {
+#pragma unroll
+        for (int mp = 0; mp < MT / 2; ++mp) {  // o-tiles 2mp, 2mp+1 -> lane row g: channels 16(2mp + (g&1)) + 8(g>>1)
+          const auto s0 = __builtin_amdgcn_permlane16_swap(ov[2 * mp][0], ov[2 * mp + 1][0], false, false);
+          const auto s1 = __builtin_amdgcn_permlane16_swap(ov[2 * mp][1], ov[2 * mp + 1][1], false, false);
+          if (live) *(u32x4*)(orow + 16 * (2 * mp + (g & 1)) + 8 * (g >> 1)) = u32x4{s0[0], s1[0], s0[1], s1[1]};
+        }
+      }
+    }
+  }
+}
+
+// Weight gradient, from dz1 = dx1 * [x1 > 0] (bf16):
+//   dW1[kappa][o] = inv_std * sum_p (img[p + tap] - mean)[ci] * dz1[p][o],   db1[o] = sum_p dz1[p][o]
+// K = pixels (chunks of 32 of a 256-pixel band), M = kappa (the ones row of db1 at kappa = K*K*3, inside the
+// padding), N = o.  dz1's band sits in LDS pixel-major (C + 8 channels a pixel) and is read with
+// ds_read_b64_tr_b16: lane (g, lx) gets channel lx of pixels 4g .. 4g + 3 and 16 + 4g .. 16 + 4g + 3 of the
+// chunk, and gathers the same 8 pixels of its kappa row from the staged image.  The MT m-tiles are dealt to the
+// 4 waves (tiles wave, wave + 4, ...), each wave over every o-tile: no cross-wave reduction.  A workgroup keeps
+// its accumulators over a contiguous run of items and writes one [dW1 | db1] slab: a fixed order of sums.
+template <int C, int W, int K, typename Tin>
+__global__ __launch_bounds__(256) void k_stem_wgrad_kxk(const Tin* __restrict__ img, const bf16* __restrict__ dz1,
+                                                        int N, int H, float mean, float inv_std,
+                                                        float* __restrict__ slabs) {
+  using G = StemK<W, K>;
+  constexpr int CIN = 3, TW = G::TW, KC = G::KC, MT = G::MT, MTW = G::MTW, NT = C / 16, BR = G::BRW;
+  constexpr int ROWS = BR + K - 1, PS = C + 8, C8 = C / 8, NPX = BR * W;
+  __shared__ float ft[ROWS * TW * CIN];
+  __shared__ __attribute__((aligned(16))) bf16 dzt[NPX * PS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, lx = lane & 15, q = lx >> 2, pq = lx & 3;
+  int koff[MTW], kind[MTW];  // kind 0: an image value, 1: the ones row, 2: padding
+#pragma unroll
+  for (int i = 0; i < MTW; ++i) {
+    const int mt = wave + 4 * i, kap = 16 * mt + lx;
+    const int kc = min(kap, KC - 1), tap = kc / CIN, ci = kc % CIN;
+    koff[i] = ((tap / K) * TW + tap % K) * CIN + ci;
+    kind[i] = (mt < MT && kap < KC) ? 0 : (mt < MT && kap == KC) ? 1 : 2;
+  }
+  f32x4 acc[MTW][NT];
+#pragma unroll
+  for (int i = 0; i < MTW; ++i)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) acc[i][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  typedef short s16x8 __attribute__((ext_vector_type(8)));
+  const int nb = (H + BR - 1) / BR;
+  const long items = (long)N * nb;
+  const long i0 = (long)blockIdx.x * items / gridDim.x, i1 = (long)(blockIdx.x + 1) * items / gridDim.x;
+  for (long item = i0; item < i1; ++item) {
+    const int n = (int)(item / nb), y0 = (int)(item % nb) * BR;
+    __syncthreads();  // the previous band fully read
+    stemk_stage<W, K, ROWS>(img, n, y0, H, mean, ft, tid);
+    const bf16* src = dz1 + ((long)n * H + y0) * W * C;  // the band's rows are contiguous: 16-B chunk i = (pixel, c8)
+    for (int i = tid; i < NPX * C8; i += 256) {
+      const int P = i / C8, c8 = i % C8;
+      uint4 v = make_uint4(0u, 0u, 0u, 0u);
+      if (y0 + P / W < H) v = *(const uint4*)(src + 8L * i);
+      *(uint4*)(dzt + P * PS + 8 * c8) = v;
+    }
+    __syncthreads();
+    const int rows = min(BR, H - y0), nch = (rows * W + 31) / 32;  // (32 nch <= NPX: every pixel read is staged)
+    for (int ch = 0; ch < nch; ++ch) {
+      const int k1 = 32 * ch + 4 * g + q;  // the pixel whose 8-B piece this lane addresses (and 16 further)
+      bf16x8 B[NT];
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ASR_LDS s16x4*)(dzt + k1 * PS + 16 * nt + 4 * pq));
+        const s16x4 b =
+            __builtin_amdgcn_ds_read_tr16_b64_v4i16((ASR_LDS s16x4*)(dzt + (k1 + 16) * PS + 16 * nt + 4 * pq));
+        const s16x8 c = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+        B[nt] = __builtin_bit_cast(bf16x8, c);
+      }
+      const int pa = 32 * ch + 4 * g, pb = pa + 16;  // this lane's two runs of 4 pixels (4 | W: each within a row)
+      const float* fa = ft + ((pa / W) * TW + pa % W) * CIN;
+      const float* fb = ft + ((pb / W) * TW + pb % W) * CIN;
+#pragma unroll
+      for (int i = 0; i < MTW; ++i) {
+        if (wave + 4 * i < MT) {  // (wave-uniform)
+          bf16x8 A;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            A[j] = (bf16)(kind[i] == 0 ? fa[CIN * j + koff[i]] : kind[i] == 1 ? 1.f : 0.f);
+            A[4 + j] = (bf16)(kind[i] == 0 ? fb[CIN * j + koff[i]] : kind[i] == 1 ? 1.f : 0.f);
+          }
+#pragma unroll
+          for (int nt = 0; nt < NT; ++nt)
+            acc[i][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B[nt], acc[i][nt], 0, 0, 0);
+        }
+      }
+    }
+  }
+  mfma_bf16_settle();
+  // D row 4g + e = kappa 16 mt + 4g + e, column lx = o 16 nt + lx; slab [dW1 (KC x C) | db1 (C)]
+  float* slab = slabs + (long)blockIdx.x * (KC * C + C);
+#pragma unroll
+  for (int i = 0; i < MTW; ++i)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int m = 16 * (wave + 4 * i) + 4 * g + e;
+        if (m <= KC) slab[m * C + 16 * nt + lx] = m < KC ? acc[i][nt][e] * inv_std : acc[i][nt][e];
+      }
 }
 
 }  // namespace blk

@@ -216,6 +216,73 @@ int stem_fwd_mfma(const void* img, int input_u8, const float* w1, const float* b
   return ASR_OK;
 }
 
+// ---------------------------------------------------------------------------
+// the 5 x 5 / 7 x 7 stem on MFMA (k_stem_fwd_kxk, k_stem_wgrad_kxk): row bands, any H
+// ---------------------------------------------------------------------------
+bool stem_kxk_supported(int K, int Cin, int W, int C) {
+  return (K == 5 || K == 7) && Cin == 3 && (W == 32 || W == 16 || W == 8) && (C == 16 || C == 32 || C == 64);
+}
+
+// every (K, C, W) of the supported set, u8 and float images
+#define ASR_STEMK_CASES(K_)                                                                                     \
+  ASR_STEMK(K_, 16, 8) ASR_STEMK(K_, 16, 16) ASR_STEMK(K_, 16, 32) ASR_STEMK(K_, 32, 8) ASR_STEMK(K_, 32, 16)   \
+  ASR_STEMK(K_, 32, 32) ASR_STEMK(K_, 64, 8) ASR_STEMK(K_, 64, 16) ASR_STEMK(K_, 64, 32)
+
+template <int C, int W, int K, typename TI>
+static int launch_stem_fwd_kxk(const void* img, const float* w1, const float* b1, int N, int H, float m, float is,
+                               void* out, hipStream_t s) {
+  const long items = (long)N * ((H + blk::StemK<W, K>::BRF - 1) / blk::StemK<W, K>::BRF);
+  const int grid = (int)std::max<long>(1, std::min<long>(items, 2L * launch_cus()));
+  hipLaunchKernelGGL((blk::k_stem_fwd_kxk<C, W, K, TI>), dim3(grid), dim3(256), 0, s, (const TI*)img, w1, b1, N, H, m,
+                     is, (bf16*)out);
+  ASR_LAUNCH_CHECK("k_stem_fwd_kxk");
+  return ASR_OK;
+}
+
+int stem_fwd_kxk(int K, const void* img, int input_u8, const float* w1, const float* b1, int N, int H, int W, int Cin,
+                 int C, float mean, float inv_std, int use_norm, void* out, hipStream_t s) {
+  if (!stem_kxk_supported(K, Cin, W, C) || N < 1 || H < 1)
+    return fail(ASR_E_UNSUPPORTED, "stem fwd (MFMA, K=%d): unsupported shape", K);
+  const float m = use_norm ? mean : 0.f, is = use_norm ? inv_std : 1.f;
+#define ASR_STEMK(K_, C_, W_)                                                                                  \
+  if (K == K_ && C == C_ && W == W_)                                                                           \
+    return input_u8 ? launch_stem_fwd_kxk<C_, W_, K_, uint8_t>(img, w1, b1, N, H, m, is, out, s)               \
+                    : launch_stem_fwd_kxk<C_, W_, K_, float>(img, w1, b1, N, H, m, is, out, s);
+  ASR_STEMK_CASES(5)
+  ASR_STEMK_CASES(7)
+#undef ASR_STEMK
+  return fail(ASR_E_UNSUPPORTED, "stem fwd (MFMA, K=%d): unsupported shape", K);
+}
+
+template <int C, int W, int K, typename TI>
+static int launch_stem_wgrad_kxk(const void* img, const void* dz1, int N, int H, float m, float is, float* slabs,
+                                 int* nslabs, hipStream_t s) {
+  const long items = (long)N * ((H + blk::StemK<W, K>::BRW - 1) / blk::StemK<W, K>::BRW);
+  const int grid = persistent_grid(items);  // (<= kMaxBlockSlabs; every workgroup has an item and writes its slab)
+  *nslabs = grid;
+  hipLaunchKernelGGL((blk::k_stem_wgrad_kxk<C, W, K, TI>), dim3(grid), dim3(256), 0, s, (const TI*)img,
+                     (const bf16*)dz1, N, H, m, is, slabs);
+  ASR_LAUNCH_CHECK("k_stem_wgrad_kxk");
+  return ASR_OK;
+}
+
+int stem_wgrad_kxk(int K, const void* img, int input_u8, const void* dz1, int N, int H, int W, int Cin, int C,
+                   float mean, float inv_std, int use_norm, float* slabs, int* nslabs, hipStream_t s) {
+  *nslabs = 0;
+  if (!stem_kxk_supported(K, Cin, W, C) || N < 1 || H < 1)
+    return fail(ASR_E_UNSUPPORTED, "stem wgrad (MFMA, K=%d): unsupported shape", K);
+  const float m = use_norm ? mean : 0.f, is = use_norm ? inv_std : 1.f;
+#define ASR_STEMK(K_, C_, W_)                                                                                  \
+  if (K == K_ && C == C_ && W == W_)                                                                           \
+    return input_u8 ? launch_stem_wgrad_kxk<C_, W_, K_, uint8_t>(img, dz1, N, H, m, is, slabs, nslabs, s)      \
+                    : launch_stem_wgrad_kxk<C_, W_, K_, float>(img, dz1, N, H, m, is, slabs, nslabs, s);
+  ASR_STEMK_CASES(5)
+  ASR_STEMK_CASES(7)
+#undef ASR_STEMK
+  return fail(ASR_E_UNSUPPORTED, "stem wgrad (MFMA, K=%d): unsupported shape", K);
+}
+#undef ASR_STEMK_CASES
+
 int block_fwd_mfma(int mode, const void* x, const void* resid, void* y, uint8_t* mask, const void* w,
                    const float* bias, float h, int N, int H, int W, int C, hipStream_t s) {
   if (W != 32) return fail(ASR_E_UNSUPPORTED, "bf16 block: W=%d not supported (W must be 32)", W);

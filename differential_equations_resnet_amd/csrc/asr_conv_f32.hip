@@ -526,8 +526,8 @@ static int launch_conv_f32(const void* xin, void* out, uint8_t* mask, const floa
 
 int conv_f32(int fmode, const void* xin, void* out, uint8_t* mask, const float* w, const float* bias, float h,
              float two_gamma, const float* dy, int N, int H, int W, int Ci, int Co, int out_bf16, hipStream_t s,
-             const float* extra) {
-  if (conv32_supported(W, Ci, Co) && fmode != F_RELU) {  // the network's blocks: fp32 MFMA
+             const float* extra, int K) {
+  if (K == 3 && conv32_supported(W, Ci, Co) && fmode != F_RELU) {  // the network's blocks: fp32 MFMA
     switch (fmode) {
       case F_EULER: return conv32_dispatch<F_EULER>(Ci, W, xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, s);
       case F_CONV: return conv32_dispatch<F_CONV>(Ci, W, xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, s);
@@ -537,17 +537,17 @@ int conv_f32(int fmode, const void* xin, void* out, uint8_t* mask, const float* 
   }
   switch (fmode) {
     case F_EULER:
-      return launch_conv_f32<float, float, F_EULER>(xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, W, Ci, Co, s);
+      return launch_conv_f32<float, float, F_EULER>(xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, W, Ci, Co, s, K);
     case F_CONV:
-      return launch_conv_f32<float, float, F_CONV>(xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, W, Ci, Co, s);
+      return launch_conv_f32<float, float, F_CONV>(xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, W, Ci, Co, s, K);
     case F_RELU:
       if (out_bf16)
-        return launch_conv_f32<float, bf16, F_RELU>(xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, W, Ci, Co, s);
-      return launch_conv_f32<float, float, F_RELU>(xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, W, Ci, Co, s);
+        return launch_conv_f32<float, bf16, F_RELU>(xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, W, Ci, Co, s, K);
+      return launch_conv_f32<float, float, F_RELU>(xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, W, Ci, Co, s, K);
     case B_EULER:
-      return launch_conv_f32<float, float, B_EULER>(xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, W, Ci, Co, s);
+      return launch_conv_f32<float, float, B_EULER>(xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, W, Ci, Co, s, K);
     case B_CONV:
-      return launch_conv_f32<float, float, B_CONV>(xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, W, Ci, Co, s);
+      return launch_conv_f32<float, float, B_CONV>(xin, out, mask, w, bias, h, two_gamma, dy, extra, N, H, W, Ci, Co, s, K);
   }
   return fail(ASR_E_ARG, "conv f32: bad mode");
 }

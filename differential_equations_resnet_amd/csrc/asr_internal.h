@@ -39,6 +39,10 @@ long theta_count(int C, int kind, int antisymmetric);
 int param_map(int C, int kind, int antisymmetric, int32_t* w_src, int32_t* theta_dst);
 int param_is_antisymmetric(int kind, int antisymmetric);
 int param_map_transpose(int C, const int32_t* w_src, int32_t* w_bwd);
+// the same for a k x k layer (odd k; the 3by3 kind has k = 3 only)
+long theta_count_k(int C, int k, int kind, int antisymmetric);
+int param_map_k(int C, int k, int kind, int antisymmetric, int32_t* w_src, int32_t* theta_dst);
+int param_map_transpose_k(int C, int k, const int32_t* w_src, int32_t* w_bwd);
 // One launch of the balanced bf16 weight pack for several layer sets (PackJob, asr_common.h)
 constexpr int kMaxPackJobs = 16;
 int theta_to_w_bf16_jobs(const PackJob* jobs, int njobs, hipStream_t s);
@@ -75,6 +79,12 @@ bool stem_wgrad_mfma_supported(int Cin, int H, int W, int C);
 int stem_fwd_mfma(const void* img, int input_u8, const float* w1, const float* b1, int N, int H, int W, int Cin, int C,
                   float mean, float inv_std, int use_norm, void* out, hipStream_t s);
 bool stem_fwd_mfma_supported(int Cin, int H, int W, int C);
+// the 5 x 5 / 7 x 7 conv1 of the bf16 networks: Cin = 3, C in {16, 32, 64}, W in {8, 16, 32}, any H
+bool stem_kxk_supported(int K, int Cin, int W, int C);
+int stem_fwd_kxk(int K, const void* img, int input_u8, const float* w1, const float* b1, int N, int H, int W, int Cin,
+                 int C, float mean, float inv_std, int use_norm, void* out, hipStream_t s);
+int stem_wgrad_kxk(int K, const void* img, int input_u8, const void* dz1, int N, int H, int W, int Cin, int C,
+                   float mean, float inv_std, int use_norm, float* slabs, int* nslabs, hipStream_t s);
 bool block_stack_fwd_supported(int N, int H, int W, int C);
 int block_stack_fwd_mfma(const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride, const void* w,
                          long w_stride, const float* bias, long bias_stride, float h, int N, int H, int W, int C, int L,
@@ -100,7 +110,7 @@ int stack_bwd_reduce_rest(const float* slabs, long slab_stride, int grid, long E
 // ---- asr_conv_f32.hip ------------------------------------------------------
 int conv_f32(int fmode, const void* xin, void* out, uint8_t* mask, const float* w, const float* bias, float h,
              float two_gamma, const float* dy, int N, int H, int W, int Ci, int Co, int out_bf16, hipStream_t s,
-             const float* extra = nullptr);
+             const float* extra = nullptr, int K = 3);
 int conv_f32_k(int fmode, int K, const void* xin, void* out, uint8_t* mask, const float* w, const float* bias, float h,
                float two_gamma, const float* dy, int N, int H, int W, int C, hipStream_t s, const float* extra);
 int make_dz(int fmode, const void* dy, const uint8_t* mask, const void* relu_src, float h, int N, int H, int W, int C,

@@ -6,8 +6,8 @@ get_single_block_resnet_build_function with one stage of identity blocks
 runs (_v6.ipynb cells 5-9):
 
     Input -> Lambda* (elementwise affine: identity / x-mean / x/std)
-          -> Conv2D 3x3 'same' stride 1 (conv1) -> relu
-          -> L x [ conv 3x3 (Conv2DAntisymmetric3By3 | Conv2DAntisymmetric(k=3) | Conv2D)
+          -> Conv2D k1 x k1 'same' stride 1 (conv1), k1 in {3, 5, 7} -> relu
+          -> L x [ conv (Conv2DAntisymmetric3By3 | Conv2DAntisymmetric(k) | Conv2D k x k, k in {3, 5, 7})
                    -> relu -> Lambda(h*x)? -> add(branch, block input) ]
           -> GlobalAveragePooling2D -> Dense(K, softmax)
 
@@ -16,7 +16,14 @@ the midpoint step built by single_layer_identity_block:
 
           xm = add(Lambda(h/2*x)?(relu(conv(x))), x);  add(Lambda(h*x)?(relu(conv(xm))), x)
 
-with the SAME conv layer applied twice.
+with the SAME conv layer applied twice (3 x 3 blocks only).
+
+All blocks share one kernel size; conv1's is free of it (the reference's
+builder passes its kernel_size to conv1 and, with kernel_type='regular', to
+every block conv; its antisymmetric blocks are the 3by3 layer).  Blocks of
+size 5 / 7 run in float32 at any shape and in bfloat16 at C in {16, 32, 64},
+W in {8, 16, 32} (asr_net_config's accepted set; the executor refuses the
+rest).
 
 With num_stages > 2 (e.g. the He-style ResNet-32, blocks [10, 10, 10] at
 32^2 x 16, 16^2 x 32, 8^2 x 64; tfkeras_resnets.py:575-593) a stage whose
@@ -26,10 +33,12 @@ filters or stride change opens with single_layer_conv_block
           add(relu(Conv2D 3x3 'same' stride s (..._branch2)), Conv2D 1x1 'valid' stride s (..._branch1))
 
 and the model lowers onto the multi-stage executor (asr_stages_*, fp32,
-Euler blocks) as a StagesPlan.
+Euler blocks) as a StagesPlan.  Multi-stage nets are 3 x 3 only: conv1, blocks
+and transitions.
 
-Anything else (BN, pooling, strided stem, non-3x3 convs, per-block differing
-h/gamma/integrator, RK2 blocks in a multi-stage net) raises AsrUnsupported
+Anything else (BN, pooling, strided stem, convs that are not square 3 / 5 / 7,
+per-block differing kernel size/h/gamma/integrator, RK2 blocks in a multi-stage
+net or at kernel size 5 / 7) raises AsrUnsupported
 naming the layer: there is no fallback executor.
 """
 from __future__ import annotations
@@ -66,6 +75,8 @@ class NetPlan:
     conv1: Conv2D = None
     blocks: list = field(default_factory=list)
     fc: Dense = None
+    kernel_size: int = 3        # the blocks' (asr_net_config.kernel_size)
+    conv1_kernel_size: int = 3  # conv1's (asr_net_config.conv1_kernel_size)
 
     def weight_vars(self):
         """Variables in the executor's flat order (Keras get_weights order)."""
@@ -181,11 +192,25 @@ def _affine_scalar(layer: Lambda, shape):
     return float(s.flat[0]), float(t.flat[0])
 
 
-def _conv3x3_same(layer: Conv2D, what):
-    if layer.kernel_size != (3, 3) or layer.strides != (1, 1) or layer.padding != "same" or not layer.use_bias:
-        raise _unsupported(layer, f"{what} must be a 3x3 'same' stride-1 conv with bias")
+NET_KERNEL_SIZES = (3, 5, 7)
+
+
+def _conv_same(layer: Conv2D, what) -> int:
+    """A square 'same' stride-1 conv with bias of size 3, 5 or 7: its size."""
+    ks = tuple(layer.kernel_size)
+    if ks[0] != ks[1] or ks[0] not in NET_KERNEL_SIZES or layer.strides != (1, 1) or layer.padding != "same" \
+            or not layer.use_bias:
+        raise _unsupported(layer, f"{what} must be a square 'same' stride-1 conv with bias of kernel size 3, 5 or 7 "
+                                  f"(kernel_size {ks})")
     if layer.dilation_rate != (1, 1):
         raise _unsupported(layer, "dilated conv")
+    return int(ks[0])
+
+
+def _block_kernel_size(conv) -> int:
+    if isinstance(conv, AntisymmetricConvBase):
+        return int(conv.kernel_size)
+    return int(conv.kernel_size[0])
 
 
 def _euler_step(t: SymbolicTensor):
@@ -205,10 +230,11 @@ def _euler_step(t: SymbolicTensor):
     conv_t = branch.inbound[0]
     conv = conv_t.layer
     if isinstance(conv, AntisymmetricConvBase):
-        if conv.kernel_size != 3 or tuple(conv.strides) != (1, 1) or not conv.use_bias:
-            raise _unsupported(conv, "antisymmetric block conv must be 3x3, stride 1, with bias")
+        if conv.kernel_size not in NET_KERNEL_SIZES or tuple(conv.strides) != (1, 1) or not conv.use_bias:
+            raise _unsupported(conv, f"antisymmetric block conv must have kernel size 3, 5 or 7 (kernel_size "
+                                     f"{conv.kernel_size}), stride 1 and a bias")
     elif isinstance(conv, Conv2D):
-        _conv3x3_same(conv, "regular block conv")
+        _conv_same(conv, "regular block conv")
         if conv.activation not in (None, "linear"):
             raise _unsupported(conv, "conv activation inside an identity block")
     else:
@@ -271,7 +297,7 @@ def analyze(model: Model) -> NetPlan:
     elif not (isinstance(t.layer, Conv2D) and t.layer.activation == "relu"):
         raise _unsupported(t.layer, "expected relu(conv1) before the first block")
     conv1 = t.layer
-    _conv3x3_same(conv1, "conv1")
+    k1 = _conv_same(conv1, "conv1")
     t = t.inbound[0]
     scale, shift = 1.0, 0.0
     while isinstance(t.layer, Lambda):
@@ -292,16 +318,27 @@ def analyze(model: Model) -> NetPlan:
               float(getattr(b, "gamma", 0.0))) for b in blocks}
     if len(kinds) != 1 or len(set(hs)) != 1 or len(set(integ)) != 1:
         raise _lib.AsrUnsupported("all identity blocks must share conv type, gamma, h and integrator")
+    kb = _block_kernel_size(first)
+    for b in blocks:
+        if _block_kernel_size(b) != kb:
+            raise _unsupported(b, f"all identity blocks must share one kernel size (kernel_size "
+                                  f"{_block_kernel_size(b)}, the first block has {kb})")
     if isinstance(first, AntisymmetricConvBase):
         kind, anti, gamma = first.param_kind, bool(first.antisymmetric), float(first.gamma)
     else:
         kind, anti, gamma = _lib.ASR_PARAM_REGULAR, False, 0.0
     if len(segs) > 1:
+        for layer, k in [(conv1, k1)] + [(b, kb) for b in blocks[:1]]:
+            if k != 3:
+                raise _unsupported(layer, f"multi-stage nets run 3x3 convs only (conv1, blocks and transitions; "
+                                          f"kernel_size {k})")
         return _stages_plan(segs, int(H), int(W), int(Cin), int(C), fc, float(hs[0]), gamma, mean, std, kind, anti,
                             integ[0], conv1)
     plan = NetPlan(H=int(H), W=int(W), Cin=int(Cin), C=int(C), L=len(blocks), num_classes=fc.units, h=float(hs[0]),
                    gamma=gamma, subtract_mean=mean, divide_by_stddev=std, param_kind=kind, antisymmetric=anti,
-                   integrator=integ[0], conv1=conv1, blocks=blocks, fc=fc)
+                   integrator=integ[0], conv1=conv1, blocks=blocks, fc=fc, kernel_size=kb, conv1_kernel_size=k1)
+    if kb != 3 and integ[0] != "euler":
+        raise _unsupported(first, f"RK2 blocks need kernel size 3 (kernel_size {kb})")
     for b in blocks:
         if b.weights[-1].shape != (C,):
             raise _unsupported(b, f"block channels must equal conv1 filters ({C})")
@@ -437,7 +474,8 @@ class NativeModel:
                                       subtract_mean=p.subtract_mean, divide_by_stddev=p.divide_by_stddev,
                                       dtype=dtype, input_u8=input_u8, device=self.device,
                                       param_kind=p.param_kind, antisymmetric=p.antisymmetric,
-                                      integrator=p.integrator, inference=inference)
+                                      integrator=p.integrator, inference=inference, kernel_size=p.kernel_size,
+                                      conv1_kernel_size=p.conv1_kernel_size)
             if ex.n_params != self.n_params:
                 raise _lib.AsrError(f"executor expects {ex.n_params} parameters, model has {self.n_params}")
             self._executors[key] = ex

@@ -417,11 +417,19 @@ class NetExecutor:
     (asr_net_* in include/asr.h).  Owns the device workspace; parameters,
     gradients and Adam moments are flat float32 buffers in Keras
     get_weights() order.  inference=True builds the forward-only workspace
-    (ASR_VARIANT_INFERENCE: x_0 and two ping-pong activation slots)."""
+    (ASR_VARIANT_INFERENCE: x_0 and two ping-pong activation slots).
+
+    kernel_size is the blocks' kernel size and conv1_kernel_size conv1's,
+    each 3, 5 or 7.  kernel_size 5 / 7 takes param_kind ASR_PARAM_GENERAL
+    (Conv2DAntisymmetric(kernel_size)) or ASR_PARAM_REGULAR, Euler blocks,
+    float32 at any shape and bfloat16 at C in {16, 32, 64}, W in {8, 16, 32};
+    such a network runs one launch per block.  conv1's size is free of the
+    blocks'.  Anything else raises AsrUnsupported (or ValueError for an even
+    size) with the accepted set in the message, before any launch."""
 
     def __init__(self, N, H, W, Cin, C, L, num_classes, h, gamma=0.0, subtract_mean=None, divide_by_stddev=None,
                  dtype="bfloat16", input_u8=True, device=None, param_kind=ASR_PARAM_3BY3, antisymmetric=True,
-                 integrator="euler", variant=0, inference=False):
+                 integrator="euler", variant=0, inference=False, kernel_size=3, conv1_kernel_size=3):
         if inference:
             variant |= ASR_VARIANT_INFERENCE
         self.device = torch.device(device) if device is not None else require_gpu()
@@ -432,7 +440,7 @@ class NetExecutor:
                              float(gamma), float(subtract_mean or 0.0),
                              float(divide_by_stddev if divide_by_stddev is not None else 1.0), int(use_norm),
                              dtype_code(dtype), int(bool(input_u8)), int(param_kind), int(bool(antisymmetric)),
-                             integrator_code(integrator), int(variant))
+                             integrator_code(integrator), int(variant), int(kernel_size), int(conv1_kernel_size))
         lib = _lib.load()
         with torch.cuda.device(self.device):  # the layout (slab rows) follows the device's CU count
             self.n_params = int(lib.asr_net_param_count(ct.byref(self.cfg)))

@@ -341,7 +341,36 @@ typedef struct asr_net_config {
   int variant;       /* 0 = the production kernel composition; ASR_VARIANT_*
                         bits select slower, independently written kernels
                         for the same math (cross-checks in the tests)      */
+  /* ABI 10 (trailing, so a zero-filled tail means the 3 x 3 network): */
+  int kernel_size;       /* the blocks' kernel size: 0 (= 3), 3, 5 or 7     */
+  int conv1_kernel_size; /* conv1's kernel size:     0 (= 3), 3, 5 or 7     */
 } asr_net_config;
+/* Accepted kernel sizes (everything else is refused before any launch, with
+ * this set in asr_last_error(): ASR_E_ARG for an even or non-positive size
+ * and for the 3by3 kind with kernel_size != 3, ASR_E_UNSUPPORTED otherwise):
+ *   - float32: conv1_kernel_size and kernel_size in {3, 5, 7} at any shape the
+ *     float32 network takes; kernel_size != 3 needs ASR_PARAM_GENERAL or
+ *     ASR_PARAM_REGULAR (Conv2DAntisymmetric(kernel_size), a regular Conv2D);
+ *   - bfloat16, kernel_size in {5, 7}: the set of asr_conv_forward_k_bf16,
+ *     C in {16, 32, 64} and W in {8, 16, 32}, any H;
+ *   - bfloat16, kernel_size 3: C in {16, 32, 64} and W == 32, as before, for
+ *     any conv1_kernel_size;
+ *   - ASR_INTEGRATOR_RK2 needs kernel_size 3 (any conv1_kernel_size);
+ *   - ASR_VARIANT_INFERENCE works for every accepted config.
+ * With both sizes 0 or 3 every call launches what it launched at ABI 9.
+ * kernel_size != 3 runs one launch per block, forward and backward (the
+ * kernels of asr_conv_forward_k / _k_bf16; W(theta) of all L layers in one
+ * asr_theta_to_w_k / _k_bf16 launch, bf16 rounded to nearest); the variant
+ * bits PER_BLOCK_*, NO_FOLD, FULL_DXL, FULL_SLABS and W_BF16 have no effect
+ * there.  conv1_kernel_size != 3: bfloat16 networks with Cin = 3, C in
+ * {16, 32, 64} and W in {8, 16, 32} run conv1 and its weight gradient on
+ * the matrix cores (k_stem_fwd_kxk / k_stem_wgrad_kxk: the 3 x 3 stem's
+ * arithmetic, bf16 (v - mean) against inv_std * W1 as bf16 hi + lo, fp32
+ * sums); float32 networks, other shapes and ASR_VARIANT_STEM_FWD_VALU /
+ * _STEM_WGRAD_VALU run a normalisation pass and the generic fp32 k x k conv /
+ * weight gradient.
+ * Parameter layout: conv1 kernel [k1,k1,Cin,C]; a block's theta count is
+ * asr_theta_count_k(C, kernel_size, param_kind, antisymmetric). */
 
 /* asr_net_config.variant bits (all 0 in production) */
 #define ASR_VARIANT_NO_FOLD 1      /* reduce every block's weight-gradient slabs in
@@ -350,7 +379,8 @@ typedef struct asr_net_config {
                                       C=64 stacked backward then has no in-launch
                                       hand-off (a cross-check arm: without it a
                                       missed hand-off degrades gracefully)       */
-#define ASR_VARIANT_STEM_FWD_VALU 2 /* bf16 stem forward on the fp32 VALU kernel  */
+#define ASR_VARIANT_STEM_FWD_VALU 2 /* bf16 stem forward on the fp32 VALU kernel
+                                       (conv1_kernel_size != 3: the generic one) */
 #define ASR_VARIANT_STEM_WGRAD_VALU 4 /* stem weight gradient on the fp32 VALU
                                         kernel from dx1 and x1 (relu' not fused
                                         into the first block's backward)       */
