@@ -22,10 +22,11 @@ static int check_shape(int N, int H, int W, int C) {
   return ASR_OK;
 }
 
-// the shapes of the bf16 3 x 3 kernels (MFMA at W = 32, the any-width convb_* at W = 16 / 8)
+// the shapes of the bf16 3 x 3 kernels (MFMA at W = 32, the any-width convb_* elsewhere: W = 16 / 8, and the
+// column-strip kernels at W >= 48)
 static int check_bf16_conv(int C, int W) {
   if (!mfma_supported(C, W) && !convb_supported(W, C))
-    return fail(ASR_E_UNSUPPORTED, "bf16 conv needs C in {16,32,64} and W in {32, 16, 8} (C=%d W=%d)", C, W);
+    return fail(ASR_E_UNSUPPORTED, "bf16 conv needs C in {16,32,64} and W == 8 or W %% 16 == 0 (C=%d W=%d)", C, W);
   return ASR_OK;
 }
 
@@ -91,7 +92,7 @@ static int block_backward(int mode, const void* dy, const void* x, const uint8_t
   if (fold_done) *fold_done = 0;
   if (dtype == ASR_BF16) {
     if (!dx && !need_w) return ASR_OK;
-    if (!mfma_supported(C, W)) {  // W = 16 / 8: the any-width bf16 kernels (plain Euler blocks and bare convs)
+    if (!mfma_supported(C, W)) {  // W != 32: the any-width bf16 kernels (plain Euler blocks and bare convs)
       if (extra || skip_dy || relu_dx || fold_slabs || accum_slabs || !convb_supported(W, C))
         return fail(ASR_E_UNSUPPORTED, "bf16 backward at C=%d W=%d: plain Euler blocks and convs only", C, W);
       return convb_backward(dy, mask, x, w, h, 2.f * gamma, N, H, W, C, dx, need_w, slabs, nsl, s,
@@ -308,7 +309,7 @@ static int net_kb(const asr_net_config* c) { return c->kernel_size ? c->kernel_s
 static const char kNetKernelSizes[] =
     "kernel_size and conv1_kernel_size in {0 (= 3), 3, 5, 7}; kernel_size 5 / 7: ASR_PARAM_GENERAL or "
     "ASR_PARAM_REGULAR blocks, Euler integrator, float32 at any shape, bfloat16 at C in {16, 32, 64} and "
-    "W in {8, 16, 32}; kernel_size 3 in bfloat16: C in {16, 32, 64} and W == 32";
+    "W in {8, 16, 32}; kernel_size 3 in bfloat16: C in {16, 32, 64} and W == 8 or W % 16 == 0 (RK2: W == 32)";
 
 static int check_net_kernel_size(const char* field, int k) {
   if (k == 3 || k == 5 || k == 7) return ASR_OK;
@@ -347,8 +348,14 @@ static int net_check(const asr_net_config* c) {
                   c->W, kNetKernelSizes);
     return ASR_OK;
   }
-  if (c->dtype == ASR_BF16 && !mfma_supported(c->C, c->W))
-    return fail(ASR_E_UNSUPPORTED, "bf16 network needs C in {16,32,64} and W == 32 (C=%d W=%d)", c->C, c->W);
+  if (c->dtype == ASR_BF16 && !mfma_supported(c->C, c->W)) {
+    // off W = 32 the blocks run one by one on the any-width kernels: plain Euler blocks only
+    if (!convb_supported(c->W, c->C))
+      return fail(ASR_E_UNSUPPORTED, "bf16 network needs C in {16,32,64} and W == 8 or W %% 16 == 0 (C=%d W=%d)", c->C,
+                  c->W);
+    if (c->integrator == ASR_INTEGRATOR_RK2)
+      return fail(ASR_E_UNSUPPORTED, "bf16 network with RK2 blocks needs W == 32 (C=%d W=%d)", c->C, c->W);
+  }
   return ASR_OK;
 }
 
@@ -597,6 +604,8 @@ static int net_forward_impl(const asr_net_config* c, const NetLayout& L, const f
     } else if (L.kxk) {
       ASR_TRY(conv_f32_k(F_EULER, L.kb, act(l), act(l + 1), mask, (const float*)wl, bias, c->h, 0.f, nullptr, N, H, W,
                          C, s, nullptr));
+    } else if (bf && !mfma_supported(C, W)) {  // W != 32: the any-width kernels (column strips at W >= 48)
+      ASR_TRY(convb_forward(act(l), act(l + 1), mask, wl, bias, c->h, N, H, W, C, s));
     } else if (bf) {
       ASR_TRY(block_fwd_mfma(0, act(l), nullptr, act(l + 1), mask, wl, bias, c->h, N, H, W, C, s));
     } else {
@@ -1298,6 +1307,9 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
       std::swap(dcur, dnext);
     }
   }
+  // bf16 off W = 32: convb_backward fuses neither the stem's relu' nor another block's slab reduction (the
+  // stem arms below apply relu' themselves, the pending reduction runs as its own launch)
+  const bool blk_fuses = !bf || mfma_supported(C, W);
   for (int l = (L.deep || stacked || L.kxk) ? -1 : cfg->L - 1; l >= 0; --l) {
     const unsigned char* wl = b + (L.sep_bwd ? L.wbuf_bwd : L.wbuf) + (size_t)l * L.wstride * L.act_bytes;
     const uint8_t* mask = (const uint8_t*)(b + L.masks) + (size_t)l * L.mask_bytes;
@@ -1319,8 +1331,9 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
     } else {
       ASR_TRY(block_backward(ASR_MODE_EULER, dcur, act(l), mask, wl, cfg->h, gam, N, H, W, C, cfg->dtype, dnext, true,
                              nullptr, false, slabs_l, (float*)(b + L.bwdws + L.bw.dz), &nsl, s,
-                             l == 0 && (L.fast_stem || L.stem_kxk) && bf && !stem_v1, l == 0 ? &dz1_fused : nullptr,
-                             fold_on ? pend_slabs : nullptr, fold_on ? pend_P : 0, pend_grp, &folded));
+                             l == 0 && (L.fast_stem || L.stem_kxk) && bf && !stem_v1 && blk_fuses,
+                             l == 0 ? &dz1_fused : nullptr, fold_on && blk_fuses ? pend_slabs : nullptr,
+                             fold_on && blk_fuses ? pend_P : 0, pend_grp, &folded));
     }
     nsl_blk = nsl;
     std::swap(dcur, dnext);

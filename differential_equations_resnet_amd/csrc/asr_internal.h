@@ -123,8 +123,11 @@ bool conv32_fused_bwd_supported(int W, int C);
 int conv32_bwd_fused(const float* dy, const uint8_t* mask, float h, const float* x, const float* w, float two_gamma,
                      const float* extra, bool skip_dy, int N, int H, int W, int C, float* dx, bool need_w,
                      float* slabs, int* nslabs, hipStream_t s);
-// bf16 Euler blocks at any stage width (W in {32, 16, 8}), the multi-stage nets' path
+// bf16 Euler blocks and bare convs at any width the 16-pixel MFMA tile takes (W = 8 or W % 16 == 0): the
+// multi-stage nets' path, and every single-stage shape off W = 32
 bool convb_supported(int W, int C);
+// slab rows one such block's weight gradient writes (the workspaces that keep every block's slabs)
+int bf16_block_slab_rows(int N, int H, int W, int C);
 int convb_forward(const void* x, void* y, uint8_t* mask, const void* w, const float* bias, float h, int N, int H, int W,
                   int C, hipStream_t s, bool conv_only = false);
 int convb_backward(const void* dy, const uint8_t* mask, const void* x, const void* w, float h, float two_gamma, int N,

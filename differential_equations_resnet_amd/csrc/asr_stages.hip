@@ -1030,8 +1030,9 @@ int stages_check(const asr_stages_config* c) {
     for (int s = 0; s < c->n_stages; ++s) {
       if (s > 0 && c->stride[s]) H = (H + c->stride[s] - 1) / c->stride[s], W = (W + c->stride[s] - 1) / c->stride[s];
       if (c->L[s] > 0 && !convb_supported(W, c->C[s]))
-        return fail(ASR_E_UNSUPPORTED, "asr_stages: bf16 stage %d needs C in {16, 32, 64} and W in {32, 16, 8} (C=%d W=%d)",
-                    s, c->C[s], W);
+        return fail(ASR_E_UNSUPPORTED,
+                    "asr_stages: bf16 stage %d needs C in {16, 32, 64} and W == 8 or W %% 16 == 0 (C=%d W=%d)", s, c->C[s],
+                    W);
       if (c->C[s] % 8) return fail(ASR_E_UNSUPPORTED, "asr_stages: bf16 stage %d: C=%d not a multiple of 8", s, c->C[s]);
     }
   }
@@ -1117,9 +1118,10 @@ SLayout stages_layout(const asr_stages_config* c) {
     g.dys = g.fused == kFusedImg ? ws.take((size_t)g.L * g.P * L.act_bytes) : 0;
     // every block keeps its slabs until the stage's one reduction launch: sized by the
     // grid the fp32 weight gradient runs at this shape, not by the 512-row maximum
-    // (deep16: its own slab rows per layer)
+    // (deep16: its own slab rows per layer; a bf16 stage on the column-strip kernels: their grid)
     g.slab_rows = g.fused == kFusedDeep16 ? (int)(deep16_slab_bytes(c->N, 1) / ((size_t)(g.E + g.C) * 4))
-                         : f32_block_slab_rows(c->N, g.H, g.W, g.C);
+                  : L.bf                  ? bf16_block_slab_rows(c->N, g.H, g.W, g.C)
+                                          : f32_block_slab_rows(c->N, g.H, g.W, g.C);
     g.grp_stride = (long)reduce_groups(g.slab_rows) * (g.E + g.C);
     g.grp = ws.take((size_t)std::max(g.L, 1) * g.grp_stride * 4);
     g.slab_stride = (long)g.slab_rows * (g.E + g.C);

@@ -424,7 +424,10 @@ class NetExecutor:
     (Conv2DAntisymmetric(kernel_size)) or ASR_PARAM_REGULAR, Euler blocks,
     float32 at any shape and bfloat16 at C in {16, 32, 64}, W in {8, 16, 32};
     such a network runs one launch per block.  conv1's size is free of the
-    blocks'.  Anything else raises AsrUnsupported (or ValueError for an even
+    blocks'.  kernel_size 3 in bfloat16 takes C in {16, 32, 64} and W == 8 or
+    any multiple of 16 (Euler blocks; RK2 at W == 32): off W == 32 the blocks
+    run one launch each, from W = 48 on the column-strip kernels.  Anything
+    else raises AsrUnsupported (or ValueError for an even
     size) with the accepted set in the message, before any launch."""
 
     def __init__(self, N, H, W, Cin, C, L, num_classes, h, gamma=0.0, subtract_mean=None, divide_by_stddev=None,
@@ -550,7 +553,7 @@ class StagesExecutor:
     (the reference's precision) or bfloat16 (the identity blocks' activations
     and convs in bf16 with fp32 accumulation; stem, transitions, head and every
     weight gradient in fp32; stages with blocks need C in {16, 32, 64} and
-    W in {32, 16, 8}).  Parameters / gradients are flat float32 buffers in the
+    W == 8 or a multiple of 16).  Parameters / gradients are flat float32 buffers in the
     asr_stages_config order; same call surface as NetExecutor."""
 
     def __init__(self, N, H, W, Cin, stages, num_classes, h, gamma=0.0, subtract_mean=None, divide_by_stddev=None,

@@ -142,6 +142,11 @@ int asr_theta_to_w(const float* theta, long theta_stride, int L, int C, const in
  *   x, y: [N,H,W,C] in dtype;  w: output of asr_theta_to_w for dtype;
  *   bias: C floats or NULL;  mask: asr_mask_bytes(N,H,W,C) bytes, relu bit of
  *   element (pixel, o) at bit index pixel*C + o (NHWC bit order, LSB first).
+ * float32 takes any shape.  bfloat16 (forward, backward and the stack calls
+ * below) takes C in {16, 32, 64} and W == 8 or W a multiple of 16 (the MFMA
+ * tile is 16 pixels of one row), any H: dedicated kernels at W in {32, 16, 8},
+ * column strips of 32 pixels (k_convbs / k_wgradbs) from W = 48 on; any other
+ * bf16 shape is ASR_E_UNSUPPORTED before any launch.
  * Replaces Conv2DAntisymmetric3By3.call (…3By3.py:157-171) and
  * single_layer_identity_block's relu/scale/add (tfkeras_resnets.py:89-92). */
 int asr_conv_forward(int mode, const void* x, void* y, uint8_t* mask, const void* w,
@@ -175,7 +180,7 @@ long asr_mask_bytes(int N, int H, int W, int C);
  * runs).  On that path the strides must keep every layer's vector accesses
  * aligned, else ASR_E_ARG before any launch: y_stride % 4, mask_stride % 2,
  * bias_stride % 4 and, in bf16, w_stride % 8.  Other shapes (bf16: C in
- * {16,32,64}, W in {32,16,8}) run the per-block kernels in sequence. */
+ * {16,32,64}, W == 8 or W % 16 == 0) run the per-block kernels in sequence. */
 int asr_block_stack_forward(const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride,
                             const void* w, long w_stride, const float* bias, long bias_stride, float h,
                             int N, int H, int W, int C, int L, int dtype, int store_all, asr_stream_t stream);
@@ -353,9 +358,14 @@ typedef struct asr_net_config {
  *     ASR_PARAM_REGULAR (Conv2DAntisymmetric(kernel_size), a regular Conv2D);
  *   - bfloat16, kernel_size in {5, 7}: the set of asr_conv_forward_k_bf16,
  *     C in {16, 32, 64} and W in {8, 16, 32}, any H;
- *   - bfloat16, kernel_size 3: C in {16, 32, 64} and W == 32, as before, for
- *     any conv1_kernel_size;
- *   - ASR_INTEGRATOR_RK2 needs kernel_size 3 (any conv1_kernel_size);
+ *   - bfloat16, kernel_size 3: C in {16, 32, 64} and W == 8 or W % 16 == 0
+ *     (asr_conv_forward's bf16 set), for any conv1_kernel_size.  W == 32 runs
+ *     what it ran before; any other width runs one launch per block, forward
+ *     and backward (Euler blocks only), conv1 on the VALU / generic arms and
+ *     the variant bits PER_BLOCK_*, NO_FOLD, FULL_DXL, FULL_SLABS have no
+ *     effect there;
+ *   - ASR_INTEGRATOR_RK2 needs kernel_size 3 (any conv1_kernel_size) and, in
+ *     bfloat16, W == 32;
  *   - ASR_VARIANT_INFERENCE works for every accepted config.
  * With both sizes 0 or 3 every call launches what it launched at ABI 9.
  * kernel_size != 3 runs one launch per block, forward and backward (the
@@ -510,7 +520,9 @@ typedef struct asr_stages_config {
  * [C[s]]); fc kernel [C_last, K], bias [K]. */
 /* ASR_OK, or the code (and asr_last_error) the calls below fail with for this
  * config: ASR_E_ARG for a malformed one, ASR_E_UNSUPPORTED for a shape the
- * kernels do not take (e.g. a bf16 stage outside C {16,32,64} x W {32,16,8}).
+ * kernels do not take (e.g. a bf16 stage with blocks outside C {16,32,64} x
+ * {W == 8 or W % 16 == 0}: asr_conv_forward's bf16 set; such stages run one
+ * launch per block off the fused stage shapes).
  * ABI 8.  Host only. */
 int asr_stages_check(const asr_stages_config* cfg);
 long asr_stages_param_count(const asr_stages_config* cfg);
