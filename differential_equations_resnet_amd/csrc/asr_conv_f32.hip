@@ -9,6 +9,8 @@
 // kernels do not cover, and for the stem conv (models/tfkeras_resnets.py:563-572,
 // a regular 3x3 conv with C_in = 3).  It shares the mask layout, the theta
 // projection and the API with the bf16 path.
+#include <type_traits>
+
 #include "asr_common.h"
 #include "asr_internal.h"
 
@@ -714,6 +716,33 @@ struct BfBand {
   static_assert(W == 8 || W == 16 || W == 32, "bf16 band: W in {8, 16, 32}");
 };
 
+// ---------------------------------------------------------------------------
+// Column strips: k_convb / k_wgradb on images wider than the one band they
+// stage, a run-time image width W >= 48, W % 16 == 0 (a 16-pixel MFMA tile
+// lies in one row).  A work item is (image, band of 4 rows, strip of SW = 32
+// columns); the LDS tiles are those of the W = 32 instantiations (6 rows x 34
+// pixels of x, 4 x 32 of dz), the two halo columns read from the neighbouring
+// strips and zero only at the image's own edges.  With W % 32 == 16 the last
+// strip has 16 columns: its columns past the image are staged as zeros, the
+// forward / dgrad skips their tiles (wave-uniform), the weight gradient runs
+// them (x and dz both zero there: the products are exactly 0, and EXEC stays
+// full for the transposed reads).  Only the global and mask-bit addresses use
+// W; the mask layout is asr.h's at any width.  A band of an image SW wide is
+// the same item with one strip (ns = 1, x0 = 0) and W = SW at compile time.
+// ---------------------------------------------------------------------------
+constexpr int kStripW = 32;
+static bool strip_width(int W) { return W >= 48 && W % 16 == 0; }
+static long strip_items(int N, int H, int W) { return (long)N * ((H + 3) / 4) * ((W + kStripW - 1) / kStripW); }
+
+// item -> image n, first row y0 and first column x0 of its band (BR rows) x strip (strips of a band adjacent)
+template <int BR, int SW>
+__device__ __forceinline__ void strip_item(long item, int nb, int ns, int& n, int& y0, int& x0) {
+  x0 = (int)(item % ns) * SW;
+  const long band = item / ns;
+  y0 = (int)(band % nb) * BR;
+  n = (int)(band / nb);
+}
+
 // 8 bf16 masked by 8 relu bits (bit j -> halfword j)
 __device__ __forceinline__ uint4 mask8_bf16(uint4 v, unsigned bits) {
   auto h2 = [&](unsigned b) { return ((b & 1u) ? 0xffffu : 0u) | ((b & 2u) ? 0xffff0000u : 0u); };
@@ -724,24 +753,27 @@ __device__ __forceinline__ uint4 mask8_bf16(uint4 v, unsigned bits) {
   return v;
 }
 
-template <int C, int W, int MODE>
+// An item is a band of 4 rows of an image SW wide, or (STRIP) a band x a strip of SW = 32 columns of an image
+// Wimg wide
+template <int C, int SW, bool STRIP, int MODE>
 __global__ __launch_bounds__(256) void k_convb(const bf16* __restrict__ xin, bf16* __restrict__ out,
                                                uint8_t* __restrict__ mask, const bf16* __restrict__ wpack,
-                                               const float* __restrict__ bias, float h, float two_gamma,
-                                               const bf16* __restrict__ dy, int N, int H,
-                                               const uint8_t* __restrict__ dmask) {
-  using G = BfBand<C, W>;
+                                               const float* __restrict__ bias, float h, float two_gamma, int N, int H,
+                                               int Wimg, const uint8_t* __restrict__ dmask) {
+  using G = BfBand<C, SW>;
+  static_assert(!STRIP || SW == kStripW, "a band x strip item is 4 x 32 pixels");
   constexpr int OT = G::OT, TW = G::TW, BR = G::BR, KS = G::KS, C8 = C / 8;
   constexpr int NCH = (BR + 2) * TW * C8, NPT = (NCH + 255) / 256;
   __shared__ __attribute__((aligned(16))) bf16 tile[G::TILEE];
-  // backward: the band's own rows of dy unmasked (the epilogue's dy term), beside the dz tile
-  __shared__ __attribute__((aligned(16))) bf16 dyc[MODE == B_EULER ? BR * W * G::PS : 8];
+  // backward: the item's own pixels of dy unmasked (the epilogue's dy term), beside the dz tile
+  __shared__ __attribute__((aligned(16))) bf16 dyc[MODE == B_EULER ? BR * SW * G::PS : 8];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, lx = lane & 15;
   const int ot = wave % OT, rw = wave / OT;
-  const int nb = (H + BR - 1) / BR;
-  const long items = (long)N * nb;
-  // persistent: a run of bands per workgroup, the W fragments loaded once, the next band's rows
-  // in registers while this band's MFMAs run
+  const int W = STRIP ? Wimg : SW;
+  const int nb = (H + BR - 1) / BR, ns = STRIP ? (W + SW - 1) / SW : 1;
+  const long items = (long)N * nb * ns;
+  // persistent: a run of items per workgroup, the W fragments loaded once, the next item's pixels
+  // in registers while this item's MFMAs run
   const long i0 = (long)blockIdx.x * items / gridDim.x, i1 = (long)(blockIdx.x + 1) * items / gridDim.x;
   bf16x8 A[KS];
 #pragma unroll
@@ -751,12 +783,13 @@ __global__ __launch_bounds__(256) void k_convb(const bf16* __restrict__ xin, bf1
   uint4 pf[NPT];
   unsigned pm[NPT];
   auto fetch = [&](long item) {
-    const int n = (int)(item / nb), y0 = (int)(item % nb) * BR;
+    int n, y0, x0;
+    strip_item<BR, SW>(item, nb, ns, n, y0, x0);
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
       const int i = tid + 256 * k;
       const int r = i / (TW * C8), rem = i % (TW * C8), col = rem / C8, c8 = rem % C8;
-      const int gy = y0 - 1 + r, gx = col - 1;
+      const int gy = y0 - 1 + r, gx = x0 - 1 + col;  // (halo columns: the neighbouring strips' pixels)
       pf[k] = make_uint4(0u, 0u, 0u, 0u);
       pm[k] = 0u;
       if (i < NCH && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) {
@@ -768,17 +801,18 @@ __global__ __launch_bounds__(256) void k_convb(const bf16* __restrict__ xin, bf1
   };
   if (i0 < i1) fetch(i0);
   for (long item = i0; item < i1; ++item) {
-    const int n = (int)(item / nb), y0 = (int)(item % nb) * BR;
-    __syncthreads();  // the previous band's tile consumed
+    int n, y0, x0;
+    strip_item<BR, SW>(item, nb, ns, n, y0, x0);
+    __syncthreads();  // the previous item's tile consumed
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
       const int i = tid + 256 * k;
       if (i >= NCH) break;
       const int r = i / (TW * C8), rem = i % (TW * C8), col = rem / C8, c8 = rem % C8;
       bf16* dst = tile + (r * TW + col) * G::PS + 8 * c8;
-      if constexpr (MODE == B_EULER) {  // the tile gets dz = dy & mask; the band's rows keep dy
+      if constexpr (MODE == B_EULER) {  // the tile gets dz = dy & mask; the item's own pixels keep dy
         *(uint4*)dst = mask8_bf16(pf[k], pm[k]);
-        if (r >= 1 && r <= BR && col >= 1 && col <= W) *(uint4*)(dyc + ((r - 1) * W + col - 1) * G::PS + 8 * c8) = pf[k];
+        if (r >= 1 && r <= BR && col >= 1 && col <= SW) *(uint4*)(dyc + ((r - 1) * SW + col - 1) * G::PS + 8 * c8) = pf[k];
       } else {
         *(uint4*)dst = pf[k];
       }
@@ -790,8 +824,10 @@ __global__ __launch_bounds__(256) void k_convb(const bf16* __restrict__ xin, bf1
     for (int j = 0; j < NT; ++j) {
       const int tau = rw + j * G::WPT;
       if (tau >= G::T) break;  // (wave-uniform)
-      const int bp = 16 * tau + lx, r = bp / W, px = bp % W;
-      if (W >= 16 && y0 + r >= H) break;  // (wave-uniform for W >= 16; rows only grow with tau)
+      const int bp = 16 * tau + lx, r = bp / SW, px = bp % SW;
+      if (SW >= 16 && y0 + r >= H) break;  // (wave-uniform for SW >= 16; rows only grow with tau)
+      if constexpr (STRIP)
+        if (x0 + 16 * (tau % (SW / 16)) >= W) continue;  // (wave-uniform: the missing half of a 16-column last strip)
       f32x4 acc = bz;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
@@ -801,8 +837,8 @@ __global__ __launch_bounds__(256) void k_convb(const bf16* __restrict__ xin, bf1
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[ks], __builtin_bit_cast(bf16x8, bv), acc, 0, 0, 0);
       }
       mfma_bf16_settle();  // (the epilogue branches: every path must see the result's wait states)
-      const bool ok = y0 + r < H;
-      const long pix = ((long)n * H + y0 + r) * W + px;
+      const bool ok = STRIP || y0 + r < H;  // (per lane only at SW = 8, where a tile spans two rows)
+      const long pix = ((long)n * H + y0 + r) * W + x0 + px;
       const long oi = pix * C + 16 * ot + 4 * g;  // this lane's 4 channels
       const uint2 cw = *(const uint2*)(tile + ((r + 1) * TW + px + 1) * G::PS + 16 * ot + 4 * g);  // x or dz at the pixel
       const float ctr[4] = {__uint_as_float(cw.x << 16), __uint_as_float(cw.x & 0xffff0000u),
@@ -829,7 +865,7 @@ __global__ __launch_bounds__(256) void k_convb(const bf16* __restrict__ xin, bf1
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = fmaf(two_gamma, ctr[e], -acc[e]);
       } else {  // B_EULER: the tile holds dz = dy & mask
-        const uint2 dw = *(const uint2*)(dyc + (r * W + px) * G::PS + 16 * ot + 4 * g);
+        const uint2 dw = *(const uint2*)(dyc + (r * SW + px) * G::PS + 16 * ot + 4 * g);
         const float d0[4] = {__uint_as_float(dw.x << 16), __uint_as_float(dw.x & 0xffff0000u),
                              __uint_as_float(dw.y << 16), __uint_as_float(dw.y & 0xffff0000u)};
         const float hg = h * two_gamma;
@@ -841,20 +877,21 @@ __global__ __launch_bounds__(256) void k_convb(const bf16* __restrict__ xin, bf1
   }
 }
 
-// W = 8, or a multiple of the 16-pixel MFMA tile: k_convb / k_wgradb at W in {32, 16, 8}, the column-strip
-// kernels (k_convbs / k_wgradbs, below) at W >= 48
+// W = 8, or a multiple of the 16-pixel MFMA tile: k_convb / k_wgradb over bands at W in {32, 16, 8}, over
+// column strips at W >= 48
 bool convb_supported(int W, int C) {
   return (W == 8 || (W >= 16 && W % 16 == 0)) && (C == 16 || C == 32 || C == 64);
 }
 
-template <int C, int W, int MODE>
+// W: the image width (= SW unless STRIP)
+template <int C, int SW, bool STRIP, int MODE>
 static int launch_convb(const bf16* xin, bf16* out, uint8_t* mask, const bf16* w, const float* bias, float h,
-                        float two_gamma, const bf16* dy, int N, int H, const uint8_t* dmask, hipStream_t s) {
-  const long items = (long)N * ((H + 3) / 4);
+                        float two_gamma, int N, int H, int W, const uint8_t* dmask, hipStream_t s) {
+  const long items = STRIP ? strip_items(N, H, W) : (long)N * ((H + 3) / 4);
   const int cus = launch_cus();
   const long grid = std::max<long>(1, std::min<long>(items, 4L * cus));  // 4 persistent workgroups per CU (r05r)
-  hipLaunchKernelGGL((k_convb<C, W, MODE>), dim3((unsigned)grid), dim3(256), 0, s, xin, out, mask, w, bias, h,
-                     two_gamma, dy, N, H, dmask);
+  hipLaunchKernelGGL((k_convb<C, SW, STRIP, MODE>), dim3((unsigned)grid), dim3(256), 0, s, xin, out, mask, w, bias, h,
+                     two_gamma, N, H, W, dmask);
   ASR_LAUNCH_CHECK("k_convb");
   return ASR_OK;
 }
@@ -900,29 +937,35 @@ __device__ __forceinline__ s16x4 tr4(const bf16* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((ASR_LDS s16x4*)p);
 }
 
-// MASKED false: dz = dy (the bare conv's weight gradient, B_CONV; dmask unused)
-template <int C, int W, bool MASKED = true>
-__global__ __launch_bounds__((WgB<C, W>::NTH)) void k_wgradb(const bf16* __restrict__ x, const bf16* __restrict__ dy,
-                                                           const uint8_t* __restrict__ dmask, int N, int H, float h,
-                                                           float* __restrict__ slabs, long x_stride, long dy_stride,
-                                                           long m_stride, long s_stride) {
-  using G = WgB<C, W>;
-  // several layers in one launch: blockIdx.y is the layer (strides in elements / bytes / floats)
-  x += blockIdx.y * x_stride;
-  dy += blockIdx.y * dy_stride;
-  dmask += blockIdx.y * m_stride;
-  slabs += blockIdx.y * s_stride;
+// An item is 128 pixels: a band of BR = 128 / SW rows of an image SW wide, or (STRIP) a band of 4 rows x a
+// strip of SW = 32 columns of an image Wimg wide (WgB<C, 32>'s tiles, waves and swizzle; a 32-pixel chunk is
+// then one row of the strip).  MASKED false: dz = dy (the bare conv's weight gradient, B_CONV; dmask unused)
+template <int C, int SW, bool STRIP, bool MASKED>
+__global__ __launch_bounds__((WgB<C, SW>::NTH)) void k_wgradb(const bf16* __restrict__ x, const bf16* __restrict__ dy,
+                                                            const uint8_t* __restrict__ dmask, int N, int H, float h,
+                                                            int Wimg, float* __restrict__ slabs, long x_stride,
+                                                            long dy_stride, long m_stride, long s_stride) {
+  using G = WgB<C, SW>;
+  static_assert(!STRIP || SW == kStripW, "a band x strip item is 4 x 32 pixels");
+  const int W = STRIP ? Wimg : SW;
+  // several layers in one launch (bands only): blockIdx.y is the layer (strides in elements / bytes / floats)
+  if constexpr (!STRIP) {
+    x += blockIdx.y * x_stride;
+    dy += blockIdx.y * dy_stride;
+    dmask += blockIdx.y * m_stride;
+    slabs += blockIdx.y * s_stride;
+  }
   constexpr int TW = G::TW, BR = G::BR, NO = G::NO, OT = G::OT, E = 9 * C * C;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_wb[];
   bf16* xt = (bf16*)lds_wb;               // [BR+2][TW][C] (chunk-swizzled per pixel)
-  bf16* dzt = xt + G::XE;                 // [BR][W][C]
+  bf16* dzt = xt + G::XE;                 // [BR][SW][C]
   float* red = (float*)(dzt + G::DE);     // [TS][ACC][64][4] (PS > 1)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, lx = lane & 15;
   const int q = lx >> 2, pq = lx & 3;
   const int ts = wave % G::TS, ps = wave / G::TS;
   const int it = ts / (OT / NO), ob = (ts % (OT / NO)) * NO;
-  const int nb = (H + BR - 1) / BR;
-  const long items = (long)N * nb;
+  const int nb = (H + BR - 1) / BR, ns = STRIP ? (W + SW - 1) / SW : 1;
+  const long items = (long)N * nb * ns;
   const long i0 = (long)blockIdx.x * items / gridDim.x, i1 = (long)(blockIdx.x + 1) * items / gridDim.x;
   f32x4 acc[9][NO], accb[NO];
 #pragma unroll
@@ -934,13 +977,14 @@ __global__ __launch_bounds__((WgB<C, W>::NTH)) void k_wgradb(const bf16* __restr
   uint4 px[G::XPT], pd[G::DPT];
   unsigned pm[G::DPT];  // the relu bits, applied at the LDS store: masking here would wait for the loads
   auto fetch = [&](long item) {
-    const int n = (int)(item / nb), y0 = (int)(item % nb) * BR;
+    int n, y0, x0;
+    strip_item<BR, SW>(item, nb, ns, n, y0, x0);
 #pragma unroll
     for (int k = 0; k < G::XPT; ++k) {
       const int i = tid + k * G::NTH;
       px[k] = make_uint4(0u, 0u, 0u, 0u);
       const int r = i / (TW * G::C8), rem = i % (TW * G::C8), col = rem / G::C8, c8 = rem % G::C8;
-      const int gy = y0 - 1 + r, gx = col - 1;
+      const int gy = y0 - 1 + r, gx = x0 - 1 + col;  // (halo columns: the neighbouring strips' pixels)
       if (i < G::XCH && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W)
         px[k] = *(const uint4*)(x + (((long)n * H + gy) * W + gx) * C + 8 * c8);
     }
@@ -949,9 +993,11 @@ __global__ __launch_bounds__((WgB<C, W>::NTH)) void k_wgradb(const bf16* __restr
       const int i = tid + k * G::NTH;
       pd[k] = make_uint4(0u, 0u, 0u, 0u);
       pm[k] = 0u;
-      const int r = i / (W * G::C8);
-      if (i < G::DCH && y0 + r < H) {
-        const long e = ((long)n * H + y0) * W * C + 8L * i;
+      const int P = i / G::C8, c8 = i % G::C8, r = P / SW, c = P % SW;
+      // (rows past the image and, in a 16-column last strip, columns past it: zeros)
+      if (i < G::DCH && y0 + r < H && (!STRIP || x0 + c < W)) {
+        // (a band's rows are contiguous in the image)
+        const long e = STRIP ? (((long)n * H + y0 + r) * W + x0 + c) * C + 8 * c8 : ((long)n * H + y0) * W * C + 8L * i;
         pd[k] = *(const uint4*)(dy + e);
         if constexpr (MASKED) pm[k] = dmask[e >> 3];
       }
@@ -987,18 +1033,19 @@ __global__ __launch_bounds__((WgB<C, W>::NTH)) void k_wgradb(const bf16* __restr
   for (int j = 0; j < 8; ++j) ones[j] = (bf16)1.f;
   if (i0 < i1) fetch(i0);
   for (long item = i0; item < i1; ++item) {
-    const int y0 = (int)(item % nb) * BR;
-    const int rows = min(BR, H - y0), nch = (rows * W + 31) / 32;
-    __syncthreads();  // the previous band's operands consumed
+    const int y0 = (int)((item / ns) % nb) * BR;
+    // a 16-column last strip's missing half runs too: x and dz are both zero there, the products exactly 0
+    const int rows = min(BR, H - y0), nch = STRIP ? rows : (rows * SW + 31) / 32;  // (32-pixel chunks: a strip's rows)
+    __syncthreads();  // the previous item's operands consumed
     store();
     __syncthreads();
-    if (item + 1 < i1) fetch(item + 1);  // in flight during this band's MFMAs
+    if (item + 1 < i1) fetch(item + 1);  // in flight during this item's MFMAs
     for (int ch = ps; ch < nch; ch += G::PS) {  // (wave-uniform: EXEC stays full for the transposed reads)
       const int k1 = 32 * ch + 4 * g + q, k2 = k1 + 16;
-      const int r1 = k1 / W, c1 = k1 % W, r2 = k2 / W, c2 = k2 % W;
+      const int r1 = k1 / SW, c1 = k1 % SW, r2 = k2 / SW, c2 = k2 % SW;
       bf16x8 B[NO];
 #pragma unroll
-      for (int o = 0; o < NO; ++o) B[o] = frag(dzt, r1 * W + c1, r2 * W + c2, ob + o);
+      for (int o = 0; o < NO; ++o) B[o] = frag(dzt, r1 * SW + c1, r2 * SW + c2, ob + o);
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
         const int d = (t / 3) * TW + t % 3;
@@ -1053,341 +1100,37 @@ __global__ __launch_bounds__((WgB<C, W>::NTH)) void k_wgradb(const bf16* __restr
   }
 }
 
-template <int C, int W, bool MASKED = true>
-static int launch_wgradb(const bf16* x, const bf16* dy, const uint8_t* mask, int N, int H, float h, float* slabs,
-                         int* nslabs, hipStream_t s, int layers = 1, long x_stride = 0, long dy_stride = 0,
-                         long m_stride = 0, long s_stride = 0) {
-  using G = WgB<C, W>;
-  const long items = (long)N * ((H + G::BR - 1) / G::BR);
-  // at most the fp32 wgrad's grid: the rows the workspaces size per block (f32_block_slab_rows)
-  // bands per workgroup (profiles/r05_he32_bf16_ab.txt; re-measured after this round's reductions:
-  // profiles/r06ai_wgradb_grid_ab.txt)
-  constexpr int minb = C == 16 ? 1 : C == 32 ? 8 : 32;
-  const int grid = (int)std::max<long>(1, std::min<long>((items + minb - 1) / minb, wgrad32_grid<C, W>(N, H)));
-  hipLaunchKernelGGL((k_wgradb<C, W, MASKED>), dim3(grid, layers), dim3(G::NTH), G::LDS, s, x, dy, mask, N, H, h, slabs,
-                     x_stride, dy_stride, m_stride, s_stride);
-  ASR_LAUNCH_CHECK("k_wgradb");
-  *nslabs = grid;
-  return ASR_OK;
-}
+// bands (128 pixels) per workgroup of k_wgradb (profiles/r05_he32_bf16_ab.txt; re-measured after round 6's
+// reductions: profiles/r06ai_wgradb_grid_ab.txt)
+static constexpr int wgradb_minb(int C) { return C == 16 ? 1 : C == 32 ? 8 : 32; }
 
-// ---------------------------------------------------------------------------
-// Column-strip variants of k_convb / k_wgradb for images wider than the one
-// band the kernels above stage: a run-time image width W >= 48, W % 16 == 0
-// (a 16-pixel MFMA tile lies in one row).  A work item is (image, band of 4
-// rows, strip of SW = 32 columns); the LDS tiles are those of the W = 32
-// instantiations (6 rows x 34 pixels of x, 4 x 32 of dz), the two halo columns
-// read from the neighbouring strips and zero only at the image's own edges.
-// With W % 32 == 16 the last strip has 16 columns: its columns past the image
-// are staged as zeros, the forward / dgrad skips their tiles (wave-uniform),
-// the weight gradient runs them (x and dz both zero there: the products are
-// exactly 0, and EXEC stays full for the transposed reads).  Only the global
-// and mask-bit addresses use W; the mask layout is asr.h's at any width.
-// ---------------------------------------------------------------------------
-constexpr int kStripW = 32;
-static bool strip_width(int W) { return W >= 48 && W % 16 == 0; }
-static long strip_items(int N, int H, int W) { return (long)N * ((H + 3) / 4) * ((W + kStripW - 1) / kStripW); }
-
-// item -> image n, first row y0 and first column x0 of its band x strip (strips of a band adjacent)
-__device__ __forceinline__ void strip_item(long item, int nb, int ns, int& n, int& y0, int& x0) {
-  x0 = (int)(item % ns) * kStripW;
-  const long band = item / ns;
-  y0 = (int)(band % nb) * 4;
-  n = (int)(band / nb);
-}
-
-template <int C, int MODE>
-__global__ __launch_bounds__(256) void k_convbs(const bf16* __restrict__ xin, bf16* __restrict__ out,
-                                                uint8_t* __restrict__ mask, const bf16* __restrict__ wpack,
-                                                const float* __restrict__ bias, float h, float two_gamma, int N, int H,
-                                                int W, const uint8_t* __restrict__ dmask) {
-  using G = BfBand<C, kStripW>;
-  constexpr int SW = kStripW, OT = G::OT, TW = G::TW, BR = G::BR, KS = G::KS, C8 = C / 8;
-  constexpr int NCH = (BR + 2) * TW * C8, NPT = (NCH + 255) / 256;
-  __shared__ __attribute__((aligned(16))) bf16 tile[G::TILEE];
-  // backward: the item's own pixels of dy unmasked (the epilogue's dy term), beside the dz tile
-  __shared__ __attribute__((aligned(16))) bf16 dyc[MODE == B_EULER ? BR * SW * G::PS : 8];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, lx = lane & 15;
-  const int ot = wave % OT, rw = wave / OT;
-  const int nb = (H + BR - 1) / BR, ns = (W + SW - 1) / SW;
-  const long items = (long)N * nb * ns;
-  // persistent, as k_convb: a run of items per workgroup, the next item's pixels in registers
-  const long i0 = (long)blockIdx.x * items / gridDim.x, i1 = (long)(blockIdx.x + 1) * items / gridDim.x;
-  bf16x8 A[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) A[ks] = *(const bf16x8*)(wpack + (((long)ot * KS + ks) * 64 + lane) * 8);
-  f32x4 bz = {0.f, 0.f, 0.f, 0.f};
-  if ((MODE == F_EULER || MODE == F_CONV) && bias) bz = *(const f32x4*)(bias + 16 * ot + 4 * g);
-  uint4 pf[NPT];
-  unsigned pm[NPT];
-  auto fetch = [&](long item) {
-    int n, y0, x0;
-    strip_item(item, nb, ns, n, y0, x0);
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-      const int i = tid + 256 * k;
-      const int r = i / (TW * C8), rem = i % (TW * C8), col = rem / C8, c8 = rem % C8;
-      const int gy = y0 - 1 + r, gx = x0 - 1 + col;  // (halo columns: the neighbouring strips' pixels)
-      pf[k] = make_uint4(0u, 0u, 0u, 0u);
-      pm[k] = 0u;
-      if (i < NCH && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) {
-        const long e = (((long)n * H + gy) * W + gx) * C + 8 * c8;
-        pf[k] = *(const uint4*)(xin + e);
-        if (MODE == B_EULER) pm[k] = dmask[e >> 3];
-      }
-    }
-  };
-  if (i0 < i1) fetch(i0);
-  for (long item = i0; item < i1; ++item) {
-    int n, y0, x0;
-    strip_item(item, nb, ns, n, y0, x0);
-    __syncthreads();  // the previous item's tile consumed
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-      const int i = tid + 256 * k;
-      if (i >= NCH) break;
-      const int r = i / (TW * C8), rem = i % (TW * C8), col = rem / C8, c8 = rem % C8;
-      bf16* dst = tile + (r * TW + col) * G::PS + 8 * c8;
-      if constexpr (MODE == B_EULER) {  // the tile gets dz = dy & mask; the item's own pixels keep dy
-        *(uint4*)dst = mask8_bf16(pf[k], pm[k]);
-        if (r >= 1 && r <= BR && col >= 1 && col <= SW) *(uint4*)(dyc + ((r - 1) * SW + col - 1) * G::PS + 8 * c8) = pf[k];
-      } else {
-        *(uint4*)dst = pf[k];
-      }
-    }
-    __syncthreads();
-    if (item + 1 < i1) fetch(item + 1);
-    constexpr int NT = (G::T + G::WPT - 1) / G::WPT;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int tau = rw + j * G::WPT;
-      if (tau >= G::T) break;  // (wave-uniform)
-      const int bp = 16 * tau + lx, r = bp / SW, px = bp % SW;
-      if (y0 + r >= H) break;                       // (wave-uniform; rows only grow with tau)
-      if (x0 + 16 * (tau % (SW / 16)) >= W) continue;  // (wave-uniform: the missing half of a 16-column last strip)
-      f32x4 acc = bz;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const int kap = 32 * ks + 8 * g;
-        const int t = min(kap / C, 8), i0c = kap - (kap / C) * C;  // (C = 16, last k-step: tap 9 pads A with zeros)
-        const uint4 bv = *(const uint4*)(tile + ((r + t / 3) * TW + px + t % 3) * G::PS + i0c);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[ks], __builtin_bit_cast(bf16x8, bv), acc, 0, 0, 0);
-      }
-      mfma_bf16_settle();  // (the epilogue branches: every path must see the result's wait states)
-      const long pix = ((long)n * H + y0 + r) * W + x0 + px;
-      const long oi = pix * C + 16 * ot + 4 * g;  // this lane's 4 channels
-      const uint2 cw = *(const uint2*)(tile + ((r + 1) * TW + px + 1) * G::PS + 16 * ot + 4 * g);  // x or dz at the pixel
-      const float ctr[4] = {__uint_as_float(cw.x << 16), __uint_as_float(cw.x & 0xffff0000u),
-                            __uint_as_float(cw.y << 16), __uint_as_float(cw.y & 0xffff0000u)};
-      float v[4];
-      if constexpr (MODE == F_EULER) {
-        unsigned nib = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float z = acc[e];
-          nib |= (z > 0.f ? 1u : 0u) << e;
-          v[e] = fmaf(h, fmaxf(z, 0.f), ctr[e]);
-        }
-        if (mask) {  // the pixel's 16 channels of this o-tile: 4 nibbles, one 16-bit store
-          unsigned m = nib << (4 * g);
-          m |= (unsigned)__shfl_xor((int)m, 16, 64);
-          m |= (unsigned)__shfl_xor((int)m, 32, 64);
-          if (g == 0) *(uint16_t*)(mask + (pix * C + 16 * ot) / 8) = (uint16_t)m;
-        }
-      } else if constexpr (MODE == F_CONV) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = acc[e];
-      } else if constexpr (MODE == B_CONV) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaf(two_gamma, ctr[e], -acc[e]);
-      } else {  // B_EULER: the tile holds dz = dy & mask
-        const uint2 dw = *(const uint2*)(dyc + (r * SW + px) * G::PS + 16 * ot + 4 * g);
-        const float d0[4] = {__uint_as_float(dw.x << 16), __uint_as_float(dw.x & 0xffff0000u),
-                             __uint_as_float(dw.y << 16), __uint_as_float(dw.y & 0xffff0000u)};
-        const float hg = h * two_gamma;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaf(hg, ctr[e], fmaf(-h, acc[e], d0[e]));
-      }
-      *(uint2*)(out + oi) = make_uint2(pk_bf16_rn(v[0], v[1]), pk_bf16_rn(v[2], v[3]));
-    }
-  }
-}
-
-template <int C, int MODE>
-static int launch_convbs(const bf16* xin, bf16* out, uint8_t* mask, const bf16* w, const float* bias, float h,
-                         float two_gamma, int N, int H, int W, const uint8_t* dmask, hipStream_t s) {
-  const long grid = std::max<long>(1, std::min<long>(strip_items(N, H, W), 4L * launch_cus()));  // as launch_convb
-  hipLaunchKernelGGL((k_convbs<C, MODE>), dim3((unsigned)grid), dim3(256), 0, s, xin, out, mask, w, bias, h, two_gamma,
-                     N, H, W, dmask);
-  ASR_LAUNCH_CHECK("k_convbs");
-  return ASR_OK;
-}
-
-// k_wgradb on a band x strip of 4 x 32 = 128 pixels per item (WgB<C, 32>'s tiles, waves and swizzle)
-template <int C, bool MASKED = true>
-__global__ __launch_bounds__((WgB<C, kStripW>::NTH)) void k_wgradbs(const bf16* __restrict__ x,
-                                                                   const bf16* __restrict__ dy,
-                                                                   const uint8_t* __restrict__ dmask, int N, int H,
-                                                                   int W, float h, float* __restrict__ slabs) {
-  using G = WgB<C, kStripW>;
-  constexpr int SW = kStripW, TW = G::TW, BR = G::BR, NO = G::NO, OT = G::OT, E = 9 * C * C;
-  static_assert(BR == 4, "a band x strip item is 4 x 32 pixels");
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_wbs[];
-  bf16* xt = (bf16*)lds_wbs;              // [BR+2][TW][C] (chunk-swizzled per pixel)
-  bf16* dzt = xt + G::XE;                 // [BR][SW][C]
-  float* red = (float*)(dzt + G::DE);     // [TS][ACC][64][4] (PS > 1)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, lx = lane & 15;
-  const int q = lx >> 2, pq = lx & 3;
-  const int ts = wave % G::TS, ps = wave / G::TS;
-  const int it = ts / (OT / NO), ob = (ts % (OT / NO)) * NO;
-  const int nb = (H + BR - 1) / BR, ns = (W + SW - 1) / SW;
-  const long items = (long)N * nb * ns;
-  const long i0 = (long)blockIdx.x * items / gridDim.x, i1 = (long)(blockIdx.x + 1) * items / gridDim.x;
-  f32x4 acc[9][NO], accb[NO];
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int o = 0; o < NO; ++o) acc[t][o] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int o = 0; o < NO; ++o) accb[o] = f32x4{0.f, 0.f, 0.f, 0.f};
-  uint4 px[G::XPT], pd[G::DPT];
-  unsigned pm[G::DPT];  // the relu bits, applied at the LDS store
-  auto fetch = [&](long item) {
-    int n, y0, x0;
-    strip_item(item, nb, ns, n, y0, x0);
-#pragma unroll
-    for (int k = 0; k < G::XPT; ++k) {
-      const int i = tid + k * G::NTH;
-      px[k] = make_uint4(0u, 0u, 0u, 0u);
-      const int r = i / (TW * G::C8), rem = i % (TW * G::C8), col = rem / G::C8, c8 = rem % G::C8;
-      const int gy = y0 - 1 + r, gx = x0 - 1 + col;
-      if (i < G::XCH && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W)
-        px[k] = *(const uint4*)(x + (((long)n * H + gy) * W + gx) * C + 8 * c8);
-    }
-#pragma unroll
-    for (int k = 0; k < G::DPT; ++k) {
-      const int i = tid + k * G::NTH;
-      pd[k] = make_uint4(0u, 0u, 0u, 0u);
-      pm[k] = 0u;
-      const int P = i / G::C8, c8 = i % G::C8, r = P / SW, c = P % SW;
-      if (i < G::DCH && y0 + r < H && x0 + c < W) {  // (rows past the image and columns past it: zeros)
-        const long e = (((long)n * H + y0 + r) * W + x0 + c) * C + 8 * c8;
-        pd[k] = *(const uint4*)(dy + e);
-        if constexpr (MASKED) pm[k] = dmask[e >> 3];
-      }
-    }
-  };
-  auto store = [&]() {
-#pragma unroll
-    for (int k = 0; k < G::XPT; ++k) {
-      const int i = tid + k * G::NTH;
-      const int P = i / G::C8, c8 = i % G::C8;
-      if (i < G::XCH) *(uint4*)(xt + P * C + 8 * (c8 ^ G::swz(P))) = px[k];
-    }
-#pragma unroll
-    for (int k = 0; k < G::DPT; ++k) {
-      const int i = tid + k * G::NTH;
-      const int P = i / G::C8, c8 = i % G::C8;
-      if (i < G::DCH) *(uint4*)(dzt + P * C + 8 * (c8 ^ G::swz(P))) = MASKED ? mask8_bf16(pd[k], pm[k]) : pd[k];
-    }
-  };
-  // the lane's 8-B piece of channels 16 ch + 4 pq .. +3 at pixel P of a tile
-  auto piece = [&](const bf16* tile, int P, int ch) {
-    const int c16 = 2 * ch + (pq >> 1);
-    return tile + P * C + 8 * (c16 ^ G::swz(P)) + 4 * (pq & 1);
-  };
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  auto frag = [&](const bf16* tile, int P1, int P2, int ch) {
-    const s16x4 a = tr4(piece(tile, P1, ch)), b = tr4(piece(tile, P2, ch));
-    const s16x8 c = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(bf16x8, c);
-  };
-  bf16x8 ones;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) ones[j] = (bf16)1.f;
-  if (i0 < i1) fetch(i0);
-  for (long item = i0; item < i1; ++item) {
-    const int y0 = (int)((item / ns) % nb) * BR;
-    const int rows = min(BR, H - y0);  // a 32-pixel chunk is one row of the strip
-    __syncthreads();  // the previous item's operands consumed
-    store();
-    __syncthreads();
-    if (item + 1 < i1) fetch(item + 1);  // in flight during this item's MFMAs
-    for (int ch = ps; ch < rows; ch += G::PS) {  // (wave-uniform: EXEC stays full for the transposed reads)
-      const int c1 = 4 * g + q, c2 = c1 + 16;
-      bf16x8 B[NO];
-#pragma unroll
-      for (int o = 0; o < NO; ++o) B[o] = frag(dzt, ch * SW + c1, ch * SW + c2, ob + o);
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int d = (t / 3) * TW + t % 3;
-        const bf16x8 A = frag(xt, ch * TW + c1 + d, ch * TW + c2 + d, it);
-#pragma unroll
-        for (int o = 0; o < NO; ++o) acc[t][o] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B[o], acc[t][o], 0, 0, 0);
-      }
-      if (it == 0) {
-#pragma unroll
-        for (int o = 0; o < NO; ++o) accb[o] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, B[o], accb[o], 0, 0, 0);
-      }
-    }
-  }
-  // the PS chunk-split partials, summed in a fixed order through LDS (one split at a time)
-  if constexpr (G::PS > 1) {
-    float* mine = red + (long)ts * G::ACC * 256;
-#pragma unroll 1
-    for (int src = 1; src < G::PS; ++src) {
-      __syncthreads();
-      if (ps == src) {
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-          for (int o = 0; o < NO; ++o) *(f32x4*)(mine + ((t * NO + o) * 64 + lane) * 4) = acc[t][o];
-#pragma unroll
-        for (int o = 0; o < NO; ++o) *(f32x4*)(mine + ((9 * NO + o) * 64 + lane) * 4) = accb[o];
-      }
-      __syncthreads();
-      if (ps == 0) {
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-          for (int o = 0; o < NO; ++o) acc[t][o] += *(const f32x4*)(mine + ((t * NO + o) * 64 + lane) * 4);
-#pragma unroll
-        for (int o = 0; o < NO; ++o) accb[o] += *(const f32x4*)(mine + ((9 * NO + o) * 64 + lane) * 4);
-      }
-    }
-  }
-  if (ps == 0) {
-    float* slab = slabs + (long)blockIdx.x * (E + C);
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-      for (int o = 0; o < NO; ++o)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          slab[((long)t * C + 16 * it + 4 * g + e) * C + 16 * (ob + o) + lx] = h * acc[t][o][e];
-    if (it == 0 && g == 0) {
-#pragma unroll
-      for (int o = 0; o < NO; ++o) slab[E + 16 * (ob + o) + lx] = h * accb[o][0];
-    }
-  }
-}
-
-// k_wgradbs's grid = its slab rows (one [dW | db] slab per workgroup), for the launcher and for every
-// workspace that keeps a block's slabs (bf16_block_slab_rows).  Items per workgroup as launch_wgradb's
+// k_wgradb's grid over column strips = its slab rows (one [dW | db] slab per workgroup), for the launcher and
+// for every workspace that keeps a block's slabs (bf16_block_slab_rows).  Items per workgroup as over bands
 // (an item is 128 pixels there too); at most two workgroups per CU and kMaxBlockSlabs rows.
 static int wgrad_strip_grid(int N, int H, int W, int C) {
   const long items = strip_items(N, H, W);
-  const int minb = C == 16 ? 1 : C == 32 ? 8 : 32;
+  const int minb = wgradb_minb(C);
   return (int)std::max<long>(1, std::min<long>({(items + minb - 1) / minb, 2L * launch_cus(), (long)kMaxBlockSlabs}));
 }
 
-template <int C, bool MASKED>
-static int launch_wgradbs(const bf16* x, const bf16* dy, const uint8_t* mask, int N, int H, int W, float h,
-                          float* slabs, int* nslabs, hipStream_t s) {
-  using G = WgB<C, kStripW>;
-  const int grid = wgrad_strip_grid(N, H, W, C);
-  hipLaunchKernelGGL((k_wgradbs<C, MASKED>), dim3(grid), dim3(G::NTH), G::LDS, s, x, dy, mask, N, H, W, h, slabs);
-  ASR_LAUNCH_CHECK("k_wgradbs");
+// W: the image width (= SW unless STRIP).  Several layers per launch over bands only.
+template <int C, int SW, bool STRIP, bool MASKED>
+static int launch_wgradb(const bf16* x, const bf16* dy, const uint8_t* mask, int N, int H, int W, float h,
+                         float* slabs, int* nslabs, hipStream_t s, int layers = 1, long x_stride = 0,
+                         long dy_stride = 0, long m_stride = 0, long s_stride = 0) {
+  using G = WgB<C, SW>;
+  int grid;
+  if constexpr (STRIP) {
+    grid = wgrad_strip_grid(N, H, W, C);
+  } else {
+    // at most the fp32 wgrad's grid: the rows the workspaces size per block (f32_block_slab_rows)
+    const long items = (long)N * ((H + G::BR - 1) / G::BR);
+    constexpr int minb = wgradb_minb(C);
+    grid = (int)std::max<long>(1, std::min<long>((items + minb - 1) / minb, wgrad32_grid<C, SW>(N, H)));
+  }
+  hipLaunchKernelGGL((k_wgradb<C, SW, STRIP, MASKED>), dim3(grid, layers), dim3(G::NTH), G::LDS, s, x, dy, mask, N, H,
+                     h, W, slabs, x_stride, dy_stride, m_stride, s_stride);
+  ASR_LAUNCH_CHECK("k_wgradb");
   *nslabs = grid;
   return ASR_OK;
 }
@@ -1398,32 +1141,40 @@ int bf16_block_slab_rows(int N, int H, int W, int C) {
   return strip_width(W) && convb_supported(W, C) ? wgrad_strip_grid(N, H, W, C) : f32_block_slab_rows(N, H, W, C);
 }
 
+// The any-width kernels' instantiation for (C, W): f(C, SW, STRIP) as integral constants, the tile width and
+// the strip flag chosen here alone -- (32, true) at a strip width, else (W, false)
+template <typename F>
+static int dispatch_c_sw(const char* what, int C, int W, F&& f) {
+  auto at_c = [&](auto c) -> int {
+    if (strip_width(W)) return f(c, std::integral_constant<int, kStripW>{}, std::true_type{});
+    switch (W) {
+      case 32: return f(c, std::integral_constant<int, 32>{}, std::false_type{});
+      case 16: return f(c, std::integral_constant<int, 16>{}, std::false_type{});
+      case 8: return f(c, std::integral_constant<int, 8>{}, std::false_type{});
+    }
+    return fail(ASR_E_UNSUPPORTED, "%s: C=%d W=%d", what, C, W);
+  };
+  switch (C) {
+    case 16: return at_c(std::integral_constant<int, 16>{});
+    case 32: return at_c(std::integral_constant<int, 32>{});
+    case 64: return at_c(std::integral_constant<int, 64>{});
+  }
+  return fail(ASR_E_UNSUPPORTED, "%s: C=%d W=%d", what, C, W);
+}
+
 // y = x + h relu(conv(x, W) + b) in bf16 (w: asr_theta_to_w's ASR_BF16 pack of one layer); with
 // conv_only the bare layer call y = conv(x, W) + b (…3By3.py:157-171; no mask, h unused)
 int convb_forward(const void* x, void* y, uint8_t* mask, const void* w, const float* bias, float h, int N, int H, int W,
                   int C, hipStream_t s, bool conv_only) {
-#define ASR_CB(CC, WW)                                                                                              \
-  if (C == CC && W == WW) {                                                                                         \
-    if (conv_only)                                                                                                  \
-      return launch_convb<CC, WW, F_CONV>((const bf16*)x, (bf16*)y, nullptr, (const bf16*)w, bias, 1.f, 0.f,        \
-                                          nullptr, N, H, nullptr, s);                                               \
-    return launch_convb<CC, WW, F_EULER>((const bf16*)x, (bf16*)y, mask, (const bf16*)w, bias, h, 0.f, nullptr, N, H, \
-                                         nullptr, s);                                                               \
-  }
-  ASR_CB(16, 32) ASR_CB(16, 16) ASR_CB(16, 8) ASR_CB(32, 32) ASR_CB(32, 16) ASR_CB(32, 8) ASR_CB(64, 32)
-  ASR_CB(64, 16) ASR_CB(64, 8)
-#undef ASR_CB
-#define ASR_CBS(CC)                                                                                                  \
-  if (C == CC && strip_width(W)) {                                                                                   \
-    if (conv_only)                                                                                                   \
-      return launch_convbs<CC, F_CONV>((const bf16*)x, (bf16*)y, nullptr, (const bf16*)w, bias, 1.f, 0.f, N, H, W,   \
-                                       nullptr, s);                                                                  \
-    return launch_convbs<CC, F_EULER>((const bf16*)x, (bf16*)y, mask, (const bf16*)w, bias, h, 0.f, N, H, W, nullptr, \
-                                      s);                                                                            \
-  }
-  ASR_CBS(16) ASR_CBS(32) ASR_CBS(64)
-#undef ASR_CBS
-  return fail(ASR_E_UNSUPPORTED, "conv bf16 (any width): C=%d W=%d", C, W);
+  return dispatch_c_sw("conv bf16 (any width)", C, W, [&](auto c, auto sw, auto strip) -> int {
+    constexpr int CC = decltype(c)::value, SW = decltype(sw)::value;
+    constexpr bool ST = decltype(strip)::value;
+    if (conv_only)
+      return launch_convb<CC, SW, ST, F_CONV>((const bf16*)x, (bf16*)y, nullptr, (const bf16*)w, bias, 1.f, 0.f, N, H,
+                                              W, nullptr, s);
+    return launch_convb<CC, SW, ST, F_EULER>((const bf16*)x, (bf16*)y, mask, (const bf16*)w, bias, h, 0.f, N, H, W,
+                                             nullptr, s);
+  });
 }
 
 // The Euler block's backward in bf16: dx = dy - h conv(dy & mask, W) + 2 gamma h (dy & mask)
@@ -1436,50 +1187,22 @@ int convb_backward(const void* dy, const uint8_t* mask, const void* x, const voi
                    bool conv_only) {
   *nslabs = 0;
   if (!convb_supported(W, C)) return fail(ASR_E_UNSUPPORTED, "conv bf16 backward (any width): C=%d W=%d", C, W);
-  if (dx) {
-#define ASR_CB(CC, WW)                                                                                                  \
-  if (C == CC && W == WW) {                                                                                             \
-    if (conv_only)                                                                                                      \
-      ASR_TRY((launch_convb<CC, WW, B_CONV>((const bf16*)dy, (bf16*)dx, nullptr, (const bf16*)w, nullptr, 1.f,        \
-                                            two_gamma, nullptr, N, H, nullptr, s)));                                   \
-    else                                                                                                                \
-      ASR_TRY((launch_convb<CC, WW, B_EULER>((const bf16*)dy, (bf16*)dx, nullptr, (const bf16*)w, nullptr, h,         \
-                                             two_gamma, (const bf16*)dy, N, H, mask, s)));                             \
-  }
-    ASR_CB(16, 32) ASR_CB(16, 16) ASR_CB(16, 8) ASR_CB(32, 32) ASR_CB(32, 16) ASR_CB(32, 8) ASR_CB(64, 32)
-    ASR_CB(64, 16) ASR_CB(64, 8)
-#undef ASR_CB
-#define ASR_CBS(CC)                                                                                                    \
-  if (C == CC && strip_width(W)) {                                                                                     \
-    if (conv_only)                                                                                                     \
-      ASR_TRY((launch_convbs<CC, B_CONV>((const bf16*)dy, (bf16*)dx, nullptr, (const bf16*)w, nullptr, 1.f, two_gamma, \
-                                         N, H, W, nullptr, s)));                                                       \
-    else                                                                                                               \
-      ASR_TRY((launch_convbs<CC, B_EULER>((const bf16*)dy, (bf16*)dx, nullptr, (const bf16*)w, nullptr, h, two_gamma,  \
-                                          N, H, W, mask, s)));                                                         \
-  }
-    ASR_CBS(16) ASR_CBS(32) ASR_CBS(64)
-#undef ASR_CBS
-  }
-  if (!need_w) return ASR_OK;
-#define ASR_WB(CC, WW)                                                                                             \
-  if (C == CC && W == WW) {                                                                                        \
-    if (conv_only)                                                                                                 \
-      return launch_wgradb<CC, WW, false>((const bf16*)x, (const bf16*)dy, nullptr, N, H, 1.f, slabs, nslabs, s); \
-    return launch_wgradb<CC, WW>((const bf16*)x, (const bf16*)dy, mask, N, H, h, slabs, nslabs, s);              \
-  }
-  ASR_WB(16, 32) ASR_WB(16, 16) ASR_WB(16, 8) ASR_WB(32, 32) ASR_WB(32, 16) ASR_WB(32, 8) ASR_WB(64, 32)
-  ASR_WB(64, 16) ASR_WB(64, 8)
-#undef ASR_WB
-#define ASR_WBS(CC)                                                                                                 \
-  if (C == CC && strip_width(W)) {                                                                                  \
-    if (conv_only)                                                                                                  \
-      return launch_wgradbs<CC, false>((const bf16*)x, (const bf16*)dy, nullptr, N, H, W, 1.f, slabs, nslabs, s);  \
-    return launch_wgradbs<CC, true>((const bf16*)x, (const bf16*)dy, mask, N, H, W, h, slabs, nslabs, s);          \
-  }
-  ASR_WBS(16) ASR_WBS(32) ASR_WBS(64)
-#undef ASR_WBS
-  return fail(ASR_E_UNSUPPORTED, "conv bf16 backward (any width): C=%d W=%d", C, W);
+  return dispatch_c_sw("conv bf16 backward (any width)", C, W, [&](auto c, auto sw, auto strip) -> int {
+    constexpr int CC = decltype(c)::value, SW = decltype(sw)::value;
+    constexpr bool ST = decltype(strip)::value;
+    if (dx) {
+      if (conv_only)
+        ASR_TRY((launch_convb<CC, SW, ST, B_CONV>((const bf16*)dy, (bf16*)dx, nullptr, (const bf16*)w, nullptr, 1.f,
+                                                  two_gamma, N, H, W, nullptr, s)));
+      else
+        ASR_TRY((launch_convb<CC, SW, ST, B_EULER>((const bf16*)dy, (bf16*)dx, nullptr, (const bf16*)w, nullptr, h,
+                                                   two_gamma, N, H, W, mask, s)));
+    }
+    if (!need_w) return ASR_OK;
+    if (conv_only)
+      return launch_wgradb<CC, SW, ST, false>((const bf16*)x, (const bf16*)dy, nullptr, N, H, W, 1.f, slabs, nslabs, s);
+    return launch_wgradb<CC, SW, ST, true>((const bf16*)x, (const bf16*)dy, mask, N, H, W, h, slabs, nslabs, s);
+  });
 }
 
 // ===========================================================================
@@ -2022,8 +1745,8 @@ int wgrad_layers(int dtype, const void* x0, long x_stride, const void* dys, long
   const bool bf = dtype == ASR_BF16;
 #define ASR_WL(CC, WW)                                                                                              \
   if (bf && C == CC && W == WW)                                                                                     \
-    return launch_wgradb<CC, WW>((const bf16*)x0, (const bf16*)dys, masks, N, H, h, slabs, nslabs, s, L, x_stride, \
-                                 d_stride, mask_stride, slab_stride);
+    return launch_wgradb<CC, WW, false, true>((const bf16*)x0, (const bf16*)dys, masks, N, H, W, h, slabs, nslabs, s, L, \
+                                              x_stride, d_stride, mask_stride, slab_stride);
 #define ASR_W32L(CC, WW)                                                                                            \
   if (!bf && C == CC && W == WW)                                                                                    \
     return launch_wgrad32<CC, WW>((const float*)x0, (const float*)dys, N, H, slabs, nslabs, s, masks, h, L, x_stride, \

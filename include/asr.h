@@ -144,8 +144,8 @@ int asr_theta_to_w(const float* theta, long theta_stride, int L, int C, const in
  *   element (pixel, o) at bit index pixel*C + o (NHWC bit order, LSB first).
  * float32 takes any shape.  bfloat16 (forward, backward and the stack calls
  * below) takes C in {16, 32, 64} and W == 8 or W a multiple of 16 (the MFMA
- * tile is 16 pixels of one row), any H: dedicated kernels at W in {32, 16, 8},
- * column strips of 32 pixels (k_convbs / k_wgradbs) from W = 48 on; any other
+ * tile is 16 pixels of one row), any H: k_convb / k_wgradb over whole rows at
+ * W in {32, 16, 8}, over column strips of 32 pixels from W = 48 on; any other
  * bf16 shape is ASR_E_UNSUPPORTED before any launch.
  * Replaces Conv2DAntisymmetric3By3.call (…3By3.py:157-171) and
  * single_layer_identity_block's relu/scale/add (tfkeras_resnets.py:89-92). */

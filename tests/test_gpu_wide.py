@@ -1,5 +1,5 @@
 """GPU parity of the bf16 3 x 3 Euler block / bare conv at image widths beyond
-32 (the column-strip kernels k_convbs / k_wgradbs: W >= 48, W % 16 == 0)
+32 (k_convb / k_wgradb over column strips: W >= 48, W % 16 == 0)
 against the numpy oracle, through every layer above them: the conv ABI, the
 stack ABI, NetExecutor, StagesExecutor, the Model API and the eager layer.
 

@@ -4,8 +4,13 @@ must: round 4's switch cleanup 6c75dab compiles every stack kernel
 bit-identically to f540cc2, the measured tree before it.)  Labels are
 renumbered, comments and directives dropped.  Prints one same/DIFF line per
 kernel (a kernel of one side only is a DIFF) and a summary; exit status 1 on
-any difference.
-usage: python tools/isa_equiv.py REV_A REV_B [source.hip ...]   (default: every product source)"""
+any difference.  --alias REGEX=REPLACEMENT (repeatable) rewrites the kernel
+symbols of both sides with re.sub before they are matched: a renamed or
+re-parameterised kernel against its predecessor.  A kernel whose instructions
+differ comes with the number of differing lines.
+usage: python tools/isa_equiv.py [--alias REGEX=REPLACEMENT ...] REV_A REV_B [source.hip ...]
+       (default: every product source)"""
+import difflib
 import os
 import re
 import subprocess
@@ -64,11 +69,29 @@ def export(rev, d):
     return dst
 
 
-def compare(tree_a, tree_b, srcs, d):
+def renamed(table, aliases):
+    """`table`'s kernel symbols after every (regex, replacement) of `aliases`"""
+    out = {}
+    for k, v in table.items():
+        for pat, rep in aliases:
+            k = re.sub(pat, rep, k)
+        assert k not in out, f"--alias maps two kernels of one side onto {k}"
+        out[k] = v
+    return out
+
+
+def differing_lines(a, b):
+    """lines in the changed blocks of a line diff (a replaced block counts its longer side)"""
+    return sum(j - i if op == "delete" else l - k if op == "insert" else max(j - i, l - k)
+               for op, i, j, k, l in difflib.SequenceMatcher(None, a, b, autojunk=False).get_opcodes()
+               if op != "equal")
+
+
+def compare(tree_a, tree_b, srcs, d, aliases=()):
     """Print one line per kernel and the summary; the number of differing kernels."""
     jobs = [(t, s, os.path.join(d, f"{i}_{s}.s")) for s in srcs for i, t in enumerate((tree_a, tree_b))]
     with ThreadPoolExecutor(min(len(jobs), os.cpu_count() or 1, 16)) as pool:
-        res = list(pool.map(lambda j: compile_tree(*j), jobs))
+        res = [tuple(renamed(t, aliases) for t in r) for r in pool.map(lambda j: compile_tree(*j), jobs)]
     total = diffs = 0
     for n, src in enumerate(srcs):
         (ka, ma), (kb, mb) = res[2 * n], res[2 * n + 1]
@@ -76,7 +99,8 @@ def compare(tree_a, tree_b, srcs, d):
             if k not in ka or k not in kb:
                 tag = "DIFF (only in %s)" % ("A" if k in ka else "B")
             elif ka[k] != kb[k]:
-                tag = "DIFF (instructions)"
+                tag = "DIFF (instructions: %d lines of %d -> %d differ)" % (differing_lines(ka[k], kb[k]), len(ka[k]),
+                                                                          len(kb[k]))
             elif k not in ma or k not in mb:
                 tag = "DIFF (no metadata entry in %s)" % " and ".join(s for s, m in (("A", ma), ("B", mb)) if k not in m)
             elif ma[k] != mb[k]:
@@ -92,6 +116,11 @@ def compare(tree_a, tree_b, srcs, d):
 
 
 if __name__ == "__main__":
-    a, b = sys.argv[1], sys.argv[2]
+    args, aliases = sys.argv[1:], []
+    while "--alias" in args:
+        i = args.index("--alias")
+        aliases.append(tuple(args[i + 1].split("=", 1)))
+        del args[i:i + 2]
+    a, b = args[0], args[1]
     with tempfile.TemporaryDirectory() as d:
-        sys.exit(1 if compare(export(a, d), export(b, d), sys.argv[3:] or SOURCES, d) else 0)
+        sys.exit(1 if compare(export(a, d), export(b, d), args[2:] or SOURCES, d, aliases) else 0)

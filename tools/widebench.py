@@ -1,5 +1,5 @@
-"""Training-step time of a single-stage 3 x 3 network at an image width off 32 (asr_net_*: bfloat16 on the
-column-strip kernels k_convbs / k_wgradbs from W = 48 on, float32 on the generic fp32 kernels).
+"""Training-step time of a single-stage 3 x 3 network at an image width off 32 (asr_net_*: bfloat16 on
+k_convb / k_wgradb over column strips from W = 48 on, float32 on the generic fp32 kernels).
 
 Each round is timed with device events over --reps steps (forward_backward + Adam) after --warmup untimed
 steps; prints the median and spread of a step as one JSON line.  --lib loads another build of libasr.so (a
