@@ -29,7 +29,7 @@ ASR_BF16 = 1
 ASR_PARAM_3BY3 = 0
 ASR_PARAM_GENERAL = 1
 ASR_PARAM_REGULAR = 2
-ABI_VERSION = 10
+ABI_VERSION = 11
 ASR_MODE_EULER = 0
 ASR_MODE_CONV = 1
 ASR_INTEGRATOR_EULER = 0
@@ -45,6 +45,9 @@ ASR_VARIANT_FULL_DXL = 128
 ASR_VARIANT_FULL_SLABS = 256
 ASR_VARIANT_W_BF16 = 512
 ASR_DIST_UNIQUE_ID_BYTES = 128
+ASR_U8 = 2
+ASR_AUG_RESIZE_NONE, ASR_AUG_RESIZE_BILINEAR, ASR_AUG_RESIZE_PAD = 0, 1, 2
+ASR_AUG_NONE, ASR_AUG_BRIGHTNESS, ASR_AUG_SATURATION = 0, 1, 2
 ASR_STAGES_MAX = 8
 
 
@@ -75,6 +78,19 @@ class StagesConfig(ct.Structure):
         ("use_norm", ct.c_int), ("input_u8", ct.c_int), ("param_kind", ct.c_int), ("antisymmetric", ct.c_int),
         ("dtype", ct.c_int),
     ]
+
+
+class AugItem(ct.Structure):
+    """asr_aug_item (include/asr.h, ABI 11): 32 bytes, one per output image."""
+    _fields_ = [("src", ct.c_int32), ("y0", ct.c_int32), ("x0", ct.c_int32), ("ch", ct.c_int32), ("cw", ct.c_int32),
+                ("flip", ct.c_int32), ("brightness", ct.c_float), ("saturation", ct.c_float)]
+
+
+class AugPlanConfig(ct.Structure):
+    """asr_aug_plan (include/asr.h, ABI 11)."""
+    _fields_ = [("Hs", ct.c_int), ("Ws", ct.c_int), ("Cch", ct.c_int), ("src_dtype", ct.c_int), ("Ho", ct.c_int),
+                ("Wo", ct.c_int), ("dst_dtype", ct.c_int), ("resize", ct.c_int), ("rh", ct.c_int), ("rw", ct.c_int),
+                ("pad_top", ct.c_int), ("pad_left", ct.c_int), ("flip_src", ct.c_int), ("color", ct.c_int * 2)]
 
 
 _P = ct.c_void_p
@@ -145,6 +161,7 @@ SIGNATURES = [
     ("asr_adam_update", _I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _L, _F, _P]),
     ("asr_segment_sq_norms", _I, [_P, _P, _I, _P, _P]),
     ("asr_batch_metrics", _I, [_P, _P, _P, _I, _I, _P, _P]),
+    ("asr_augment_batch", _I, [_P, _L, ct.POINTER(AugPlanConfig), _P, _I, _P, _P]),
     ("asr_dist_unique_id", _I, [_P]),
     ("asr_dist_init", _I, [_I, _I, _P]),
     ("asr_dist_allreduce_sum", _I, [_P, _S, _I, _P]),

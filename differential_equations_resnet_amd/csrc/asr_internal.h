@@ -178,6 +178,11 @@ int head(const void* xL, int act_bf16, const float* fck, const float* fcb, const
 int head_param_grads(const float* gap, const float* dlogits, int N, int C, int K, float* dfck, float* dfcb,
                      const float* loss_per, float* loss_out, hipStream_t s);
 
+// ---- asr_augment.hip -------------------------------------------------------
+// the dataset preprocessors in one launch per batch (asr_augment_batch, asr.h, is this with a void* stream)
+int augment_batch(const void* src, long n_src, const asr_aug_plan* plan, const asr_aug_item* items, int N, void* dst,
+                  hipStream_t s);
+
 // ---- asr_api.hip -----------------------------------------------------------
 int conv_backward_keep_slabs(const void* dy, const void* x, const uint8_t* mask, const void* w, float h, float gamma,
                              int N, int H, int W, int C, void* dx, void* ws, float* slabs, int* nsl, hipStream_t s);

@@ -22,7 +22,7 @@ __all__ = [
     "require_gpu", "dtype_code", "torch_dtype", "ParamMap", "param_map", "theta_count", "theta_to_w",
     "conv_forward", "block_stack_forward", "block_stack_backward", "conv_backward", "rk2_forward", "rk2_backward",
     "integrator_code", "NetExecutor", "adam_update", "stack_status", "transition_forward", "transition_backward",
-    "StagesExecutor",
+    "StagesExecutor", "augment_batch",
 ]
 
 
@@ -46,9 +46,12 @@ def integrator_code(integrator) -> int:
     raise ValueError(f"unknown integrator {integrator!r} ('euler' or 'rk2')")
 
 
+NO_GPU = "a gfx950 (MI355X) HIP device is required: libasr has no CPU path"
+
+
 def require_gpu() -> torch.device:
     if not torch.cuda.is_available():
-        raise _lib.AsrError("a gfx950 (MI355X) HIP device is required: libasr has no CPU path")
+        raise _lib.AsrError(NO_GPU)
     _lib.load()
     return torch.device("cuda", torch.cuda.current_device())
 
@@ -410,6 +413,39 @@ def rk2_stack_backward(dyL, x0, ys, xmids, masks1, masks2, w, pmap: ParamMap, h:
 def adam_update(params, grads, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
     _lib.call("asr_adam_update", _p(params), _p(grads), _p(m), _p(v), params.numel(), float(lr), float(beta1),
               float(beta2), float(eps), int(step), float(grad_scale), _stream())
+
+
+def augment_batch(features, plan, items, out=None):
+    """One augmented batch in one launch (asr_augment_batch): row items[i].src of the device
+    dataset array `features` [n, Hs, Ws, C] (uint8 or float32) through the compiled chain `plan`
+    (dataset_utils AugPlan) with the parameters of table row i.  `items` is the device copy of
+    the table (any tensor of N * 32 bytes in asr_aug_item layout); it must hold in-range values
+    (the kernel clamps, it does not report).  Returns [N, Ho, Wo, C] in the plan's output dtype."""
+    if not (features.is_cuda and items.is_cuda):
+        raise ValueError("augment_batch: features and items must be device tensors")
+    if not (features.is_contiguous() and items.is_contiguous()):
+        raise ValueError("augment_batch: features and items must be contiguous")
+    Hs, Ws, C = plan.in_shape
+    want = torch.uint8 if np.dtype(plan.in_dtype) == np.uint8 else torch.float32
+    if features.dtype != want or tuple(features.shape[1:]) != (Hs, Ws, C):
+        raise ValueError(f"augment_batch: the plan was compiled for {plan.in_dtype} images {(Hs, Ws, C)}, got "
+                         f"{features.dtype} {tuple(features.shape[1:])}")
+    nbytes = items.numel() * items.element_size()
+    if nbytes == 0 or nbytes % ct.sizeof(_lib.AugItem):
+        raise ValueError(f"augment_batch: the table holds {nbytes} bytes, not a positive multiple of 32")
+    N = nbytes // ct.sizeof(_lib.AugItem)
+    Ho, Wo, _ = plan.out_shape
+    out_u8 = np.dtype(plan.out_dtype) == np.uint8
+    if out is None:
+        out = torch.empty((N, Ho, Wo, C), dtype=torch.uint8 if out_u8 else torch.float32, device=features.device)
+    color = list(plan.color) + [_lib.ASR_AUG_NONE] * (2 - len(plan.color))
+    cfg = _lib.AugPlanConfig(Hs, Ws, C, _lib.ASR_U8 if want == torch.uint8 else ASR_F32, Ho, Wo,
+                             _lib.ASR_U8 if out_u8 else ASR_F32, int(plan.resize), int(plan.resized[0]),
+                             int(plan.resized[1]), int(plan.pad[0]), int(plan.pad[1]), int(bool(plan.flip_src)),
+                             (ct.c_int * 2)(*color))
+    _lib.call("asr_augment_batch", _p(features), int(features.shape[0]), ct.byref(cfg), _p(items), int(N), _p(out),
+              _stream())
+    return out
 
 
 class NetExecutor:

@@ -559,6 +559,96 @@ int asr_batch_metrics(const float* probs, const float* targets, const float* los
                       float* accum, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Device-side image augmentation (ABI 11): the reference's dataset
+ * preprocessors (dataset_utils/tf_dataset_preprocessors_image_classification.py:
+ * RandomCrop, Resize, ResizeWithPad, RandomFlipLeftRight, RandomBrightness,
+ * RandomSaturation) applied while a batch is gathered from the dataset array
+ * in HBM: one launch per batch does gather by index -> crop -> bilinear resize
+ * (or resize with zero padding) -> left-right flip -> colour operations, with
+ * no intermediate tensor and no host synchronisation.  Nothing random happens
+ * on the device: the host draws one asr_aug_item per output image and the
+ * kernel applies it, so the batch is a pure function of the table.
+ *
+ * Semantics are those of the TF 1.12 calls the reference makes:
+ *   crop      output window [y0, y0+ch) x [x0, x0+cw) of source row src
+ *             (tf.image.random_crop);
+ *   resize    tf.image.resize_images, bilinear, align_corners=False, legacy
+ *             coordinates: output index d reads source coordinate
+ *             s = d * (in / out), lo = floor(s), hi = min(lo + 1, in - 1),
+ *             f = s - lo; top = tl + (tr - tl) * fx, bottom likewise,
+ *             out = top + (bottom - top) * fy; float32 arithmetic, float32
+ *             output on the input's scale (0..255 from uint8);
+ *   pad       tf.image.resize_image_with_pad: the window resized to rh x rw
+ *             sits at (pad_top, pad_left) of the Ho x Wo output, zeros
+ *             elsewhere (the caller computes the extent and offsets);
+ *   flip      output column x reads column Wo - 1 - x; with flip_src the
+ *             crop window's columns are mirrored before the resize instead
+ *             (a flip listed before the resize: the legacy coordinates are
+ *             not symmetric, so the two differ);
+ *   brightness  tf.image.adjust_brightness: float32 x + delta, unclipped;
+ *             uint8 x * (1/255) + delta, then back as convert_image_dtype
+ *             (saturate): * 255.5, clamp to [0, 255], truncate;
+ *   saturation  tf.image.adjust_saturation, 3 channels: v = max(r,g,b),
+ *             range = v - min(r,g,b), s = v > 0 ? range / v : 0; for
+ *             range > 0, n = 1 / (6 range) and h = n (g - b) if r == v, else
+ *             n (b - r) + 2/6 if g == v, else n (r - g) + 4/6, h += 1 if
+ *             h < 0 (h = 0 for range <= 0); s <- clip(s * factor, 0, 1);
+ *             c = s v, m = v - c, d = 6 h, x = c (1 - |d mod 2 - 1|),
+ *             k = int(d) mod 6: (r,g,b) = m + (c,x,0), (x,c,0), (0,c,x),
+ *             (0,x,c), (x,0,c), (c,0,x) for k = 0..5.  uint8 images go
+ *             through the same [0, 1] conversion and back, per operation.
+ * Output dtype: uint8 when the source is uint8 and no resize runs, float32
+ * otherwise.
+ * ---------------------------------------------------------------------- */
+#define ASR_U8 2 /* image dtype of the augmentation (with ASR_F32) */
+
+#define ASR_AUG_RESIZE_NONE 0     /* Ho x Wo is the crop window itself         */
+#define ASR_AUG_RESIZE_BILINEAR 1 /* window ch x cw -> Ho x Wo                 */
+#define ASR_AUG_RESIZE_PAD 2      /* window ch x cw -> rh x rw inside Ho x Wo  */
+
+#define ASR_AUG_NONE 0
+#define ASR_AUG_BRIGHTNESS 1
+#define ASR_AUG_SATURATION 2
+
+/* One output image's parameters (32 bytes; a device array of N of them). */
+typedef struct asr_aug_item {
+  int32_t src;        /* row of the dataset array                             */
+  int32_t y0, x0;     /* crop window origin in the source image              */
+  int32_t ch, cw;     /* crop window size (ignored without a resize: Ho, Wo) */
+  int32_t flip;       /* 0 or 1                                               */
+  float brightness;   /* the delta                                            */
+  float saturation;   /* the factor                                           */
+} asr_aug_item;
+
+/* One call's description (host). */
+typedef struct asr_aug_plan {
+  int Hs, Ws, Cch;    /* source images [n_src, Hs, Ws, Cch]; Cch 1 or 3      */
+  int src_dtype;      /* ASR_U8 or ASR_F32                                    */
+  int Ho, Wo;         /* output images [N, Ho, Wo, Cch]                       */
+  int dst_dtype;      /* ASR_U8 (uint8 source, no resize) or ASR_F32          */
+  int resize;         /* ASR_AUG_RESIZE_*                                     */
+  int rh, rw;         /* ASR_AUG_RESIZE_PAD: the resized extent ...           */
+  int pad_top, pad_left; /* ... and its offset in the output                 */
+  int flip_src;       /* mirror the crop window, not the output (see above)   */
+  int color[2];       /* ASR_AUG_* in the order they run; ASR_AUG_NONE skips  */
+} asr_aug_plan;
+
+/* dst[i] = augment(src[items[i].src], items[i]) for i < N, on the caller's
+ * stream.  src: the dataset array (n_src rows); dst: 16-B aligned.
+ * Checked on the host before any launch: null pointers, N < 1, sizes < 1, a
+ * window (no resize: Ho x Wo) larger than the source, a padded extent outside
+ * the output, an unknown resize mode or colour operation and a dst_dtype other
+ * than the rule above give ASR_E_ARG; a channel count other than 1 or 3,
+ * saturation on one channel, an unknown dtype and 2^31 or more output pixels
+ * give ASR_E_UNSUPPORTED with the value in asr_last_error().
+ * The device table is NOT validated on the host (no synchronisation): items
+ * must hold 0 <= src < n_src and windows inside the source.  The kernel clamps
+ * src, the window size and its origin into the array, so a bad table gives
+ * wrong pixels, never an access outside src. */
+int asr_augment_batch(const void* src, long n_src, const asr_aug_plan* plan, const asr_aug_item* items, int N,
+                      void* dst, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Data-parallel collectives (RCCL over xGMI; one process per GPU).  NEW: the
  * reference is single-device (experiments_antisymmetric_resnet_v6.ipynb:361);
  * SURVEY.md §8(e) adds one all-reduce of the flat fp32 gradient buffer per
