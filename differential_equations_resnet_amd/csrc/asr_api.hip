@@ -26,7 +26,8 @@ static int check_shape(int N, int H, int W, int C) {
 // column-strip kernels at W >= 48)
 static int check_bf16_conv(int C, int W) {
   if (!mfma_supported(C, W) && !convb_supported(W, C))
-    return fail(ASR_E_UNSUPPORTED, "bf16 conv needs C in {16,32,64} and W == 8 or W %% 16 == 0 (C=%d W=%d)", C, W);
+    return fail(ASR_E_UNSUPPORTED, "bf16 conv needs C in {16,32,64,128,256} and W == 8 or W %% 16 == 0 (C=%d W=%d)", C,
+                W);
   return ASR_OK;
 }
 
@@ -50,7 +51,9 @@ static BwdWs bwd_ws_layout(int N, int H, int W, int C, int dtype, int stages = 1
   BwdWs b{};
   const long E = (long)K * K * C * C;
   const long P = (long)N * H * W * C;
-  const int nsl = slab_rows >= 0 ? slab_rows : kMaxBlockSlabs * stages;
+  // bf16 at C in {128, 256} (k_wgradbw): the rows its grid writes (a row is 0.6 / 2.4 MB), not the 512-row maximum
+  const bool wide = dtype == ASR_BF16 && K == 3 && C > 64 && convb_supported(W, C);
+  const int nsl = slab_rows >= 0 ? slab_rows : (wide ? bf16_block_slab_rows(N, H, W, C) : kMaxBlockSlabs) * stages;
   WsCursor c;
   b.dz = c.take(dtype == ASR_F32 ? (size_t)P * 4 : 0);
   b.slabs = c.take((size_t)nsl * (E + C) * 4);
@@ -309,7 +312,8 @@ static int net_kb(const asr_net_config* c) { return c->kernel_size ? c->kernel_s
 static const char kNetKernelSizes[] =
     "kernel_size and conv1_kernel_size in {0 (= 3), 3, 5, 7}; kernel_size 5 / 7: ASR_PARAM_GENERAL or "
     "ASR_PARAM_REGULAR blocks, Euler integrator, float32 at any shape, bfloat16 at C in {16, 32, 64} and "
-    "W in {8, 16, 32}; kernel_size 3 in bfloat16: C in {16, 32, 64} and W == 8 or W % 16 == 0 (RK2: W == 32)";
+    "W in {8, 16, 32}; kernel_size 3 in bfloat16: C in {16, 32, 64, 128, 256} and W == 8 or W % 16 == 0 (RK2: W == 32, "
+    "C <= 64)";
 
 static int check_net_kernel_size(const char* field, int k) {
   if (k == 3 || k == 5 || k == 7) return ASR_OK;
@@ -351,10 +355,11 @@ static int net_check(const asr_net_config* c) {
   if (c->dtype == ASR_BF16 && !mfma_supported(c->C, c->W)) {
     // off W = 32 the blocks run one by one on the any-width kernels: plain Euler blocks only
     if (!convb_supported(c->W, c->C))
-      return fail(ASR_E_UNSUPPORTED, "bf16 network needs C in {16,32,64} and W == 8 or W %% 16 == 0 (C=%d W=%d)", c->C,
-                  c->W);
+      return fail(ASR_E_UNSUPPORTED,
+                  "bf16 network needs C in {16,32,64,128,256} and W == 8 or W %% 16 == 0 (C=%d W=%d)", c->C, c->W);
     if (c->integrator == ASR_INTEGRATOR_RK2)
-      return fail(ASR_E_UNSUPPORTED, "bf16 network with RK2 blocks needs W == 32 (C=%d W=%d)", c->C, c->W);
+      return fail(ASR_E_UNSUPPORTED, "bf16 network with RK2 blocks needs W == 32 and C in {16,32,64} (C=%d W=%d)", c->C,
+                  c->W);
   }
   return ASR_OK;
 }
@@ -410,13 +415,15 @@ static NetLayout net_layout(const asr_net_config* c) {
   const bool f32 = c->dtype == ASR_F32;
   L.kxk_rows = !L.kxk ? 0 : f32 ? wgrad_f32_chunks(c->N, c->H) : wgradk_bf16_slab_rows(L.kb, c->N, c->H, c->W, C);
   L.f32_rows = f32 && !L.kxk ? f32_block_slab_rows(c->N, c->H, c->W, C) : 0;
+  // bf16 blocks at C in {128, 256}: every slab area by the rows k_wgradbw writes (Euler only there: one stage)
+  const int bf_rows = !f32 && !L.kxk && C > 64 ? bf16_block_slab_rows(c->N, c->H, c->W, C) : kMaxBlockSlabs;
   L.bw = bwd_ws_layout(c->N, c->H, c->W, C, c->dtype, L.stages, L.kb, L.kxk ? L.kxk_rows : f32 ? 0 : -1);
   L.stem = stem_ws_layout(L.P, c->Cin, C, L.k1);
   L.bwdws = ws.take(tr ? std::max(L.bw.total, L.stem.total) : 0);
   // odd Euler blocks' slabs (even ones use the backward workspace's): a
   // block's slabs stay readable while the next block's kernel reduces them
-  L.slabs2 = ws.take(tr && !f32 && !L.kxk ? (size_t)L.stages * kMaxBlockSlabs * (L.E + C) * 4 : 0);  // every other block's slabs
-  const int rows = L.kxk ? L.kxk_rows : f32 ? L.stages * L.f32_rows : L.stages * kMaxBlockSlabs;
+  L.slabs2 = ws.take(tr && !f32 && !L.kxk ? (size_t)L.stages * bf_rows * (L.E + C) * 4 : 0);  // every other block's slabs
+  const int rows = L.kxk ? L.kxk_rows : f32 ? L.stages * L.f32_rows : L.stages * bf_rows;
   L.grp_stride = (long)reduce_groups(rows) * (L.E + C);
   L.grp = ws.take(tr ? (size_t)c->L * L.grp_stride * 4 : 0);
   L.slab_stride = (long)rows * (L.E + C);

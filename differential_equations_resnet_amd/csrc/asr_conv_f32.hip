@@ -877,10 +877,14 @@ __global__ __launch_bounds__(256) void k_convb(const bf16* __restrict__ xin, bf1
   }
 }
 
+// C in {128, 256}: k_convbw / k_wgradbw (below), the same items with W streamed from its pack
+static bool wide_c(int C) { return C == 128 || C == 256; }
+static int wgrad_wide_rows(int N, int H, int W, int C);
+
 // W = 8, or a multiple of the 16-pixel MFMA tile: k_convb / k_wgradb over bands at W in {32, 16, 8}, over
 // column strips at W >= 48
 bool convb_supported(int W, int C) {
-  return (W == 8 || (W >= 16 && W % 16 == 0)) && (C == 16 || C == 32 || C == 64);
+  return (W == 8 || (W >= 16 && W % 16 == 0)) && (C == 16 || C == 32 || C == 64 || wide_c(C));
 }
 
 // W: the image width (= SW unless STRIP)
@@ -1138,7 +1142,377 @@ static int launch_wgradb(const bf16* x, const bf16* dy, const uint8_t* mask, int
 // Slab rows one bf16 3x3 block's weight gradient writes on the any-width kernels (convb_backward): the
 // strip grid at W >= 48, else at most the fp32 MFMA grid (launch_wgradb)
 int bf16_block_slab_rows(int N, int H, int W, int C) {
+  if (wide_c(C) && convb_supported(W, C)) return wgrad_wide_rows(N, H, W, C);  // (k_wgradbw's pixel splits)
   return strip_width(W) && convb_supported(W, C) ? wgrad_strip_grid(N, H, W, C) : f32_block_slab_rows(N, H, W, C);
+}
+
+// ===========================================================================
+// bf16 blocks at C in {128, 256} (k_convbw / k_wgradbw): k_convb's items, tiles,
+// fragment maps and epilogue, but an o-tile's KS = 9C/32 A fragments (144 / 288
+// VGPRs) no longer fit in registers, and k_wgradb's 9 (C/16)^2 accumulator
+// tiles no longer fit in a workgroup.
+// Forward / dgrad (k_convbw): 8 waves; a wave owns a pair of o-tiles (one B read
+// from LDS feeds two MFMAs) and every 16-pixel tile of one item: 2 x NTW <= 16
+// accumulators.  C = 256 has 8 pairs: a workgroup runs one item per pass over
+// the pack.  C = 128 has 4: it stages two items and runs them in one pass (wave
+// = pair x item), which halves the pack bytes read per item.  A wave streams its
+// pair's A fragments from the pack (L2-resident) in chunks of KQ = 4 k-steps (2
+// where it holds 16 accumulators: registers), the next chunk's loads in flight
+// during this chunk's MFMAs.  The LDS tile of an item is k_convb's (6 x (SW + 2)
+// pixels, C + 8 elements a pixel: 55.5 KB at C = 128, twice that for the pass's
+// two items; 107.7 KB at 256); B_EULER takes the epilogue's dy
+// term from global memory (the item has just read it), so only the dz tile
+// lives in LDS.
+// Weight gradient (k_wgradbw): k_wgradb's C = 64 geometry on a (i-block,
+// o-block) pair of 64 x 64 channels, blockIdx.y = ib * (C/64) + ob: the
+// workgroup stages those 128-B slices of x and dz, walks its share (blockIdx.x
+// of gridDim.x pixel splits) of the 128-pixel items and writes its block of slab
+// row blockIdx.x; db from the ib = 0 workgroups.
+// ===========================================================================
+template <int C, int SW>
+struct BfWide {
+  static constexpr int OT = C / 16, TW = SW + 2, BR = 4, PS = C + 8, TILEE = (BR + 2) * TW * PS;
+  static constexpr int T = BR * SW / 16;  // 16-pixel tiles per item
+  static constexpr int NW = 8, NTH = 64 * NW;
+  // o-tile pairs; items per pass over W (a wave per pair and item); tiles per wave: all of its item's
+  static constexpr int NOP = OT / 2, IPP = NW / NOP, NTW = T;
+  static constexpr int KS = 9 * C / 32, KQ = NTW == 8 ? 2 : 4, NQ = KS / KQ, QT = C / 32 / KQ;  // k-steps, chunk, chunks, chunks per tap
+  static constexpr int C8 = C / 8, NCH = (BR + 2) * TW * C8, NPT = (NCH + NTH - 1) / NTH;
+  static constexpr int NPT4 = (NPT + 3) / 4 * 4;  // staging: groups of 4 chunks per thread (the tail past NCH idle)
+  static constexpr size_t LDS = (size_t)IPP * TILEE * 2;
+  static_assert(C == 128 || C == 256, "wide bf16 band: C in {128, 256}");
+  static_assert(SW == 8 || SW == 16 || SW == 32, "wide bf16 band: W in {8, 16, 32}");
+  static_assert(NOP * IPP == NW && NQ * KQ == KS && QT * KQ * 32 == C && LDS <= 160 * 1024, "wide bf16 band: geometry");
+};
+
+template <int C, int SW, bool STRIP, int MODE>
+__global__ __launch_bounds__(512) void k_convbw(const bf16* __restrict__ xin, bf16* __restrict__ out,
+                                                uint8_t* __restrict__ mask, const bf16* __restrict__ wpack,
+                                                const float* __restrict__ bias, float h, float two_gamma, int N, int H,
+                                                int Wimg, const uint8_t* __restrict__ dmask) {
+  using G = BfWide<C, SW>;
+  static_assert(!STRIP || SW == kStripW, "a band x strip item is 4 x 32 pixels");
+  constexpr int TW = G::TW, BR = G::BR, KS = G::KS, C8 = G::C8, NTW = G::NTW, PS = G::PS, KQ = G::KQ, NQ = G::NQ;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_cw[];
+  // [IPP][BR+2][TW][PS]: x, or dz = dy & mask (B_EULER), of the pass's items; this wave's item is ph
+  bf16* tile = (bf16*)lds_cw + (threadIdx.x >> 6) / G::NOP * G::TILEE;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, lx = lane & 15;
+  const int ot0 = 2 * (wave % G::NOP), ph = wave / G::NOP;
+  const int W = STRIP ? Wimg : SW;
+  const int nb = (H + BR - 1) / BR, ns = STRIP ? (W + SW - 1) / SW : 1;
+  const long items = (long)N * nb * ns;
+  // persistent over passes of IPP items
+  const long passes = (items + G::IPP - 1) / G::IPP;
+  const long i0 = (long)blockIdx.x * passes / gridDim.x * G::IPP;
+  const long i1 = min(items, (long)(blockIdx.x + 1) * passes / gridDim.x * G::IPP);
+  f32x4 bz[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  if ((MODE == F_EULER || MODE == F_CONV) && bias) {
+#pragma unroll
+    for (int o = 0; o < 2; ++o) bz[o] = *(const f32x4*)(bias + 16 * (ot0 + o) + 4 * g);
+  }
+  // fragment (ot, ks) of the pack: 1 KB at ((ot KS + ks) 64 + lane) 8
+  const bf16* wl = wpack + ((long)ot0 * KS * 64 + lane) * 8;
+  // lane lx's pixel of tile tau is item pixel 16 tau + lx
+  int tb[NTW], trow[NTW], tpx[NTW];
+#pragma unroll
+  for (int j = 0; j < NTW; ++j) {
+    const int bp = 16 * j + lx;
+    trow[j] = bp / SW;
+    tpx[j] = bp % SW;
+    tb[j] = (trow[j] * TW + tpx[j]) * PS + 8 * g;
+  }
+  for (long base = i0; base < i1; base += G::IPP) {
+    __syncthreads();  // the previous pass's tiles consumed
+    // stage rows y0-1 .. y0+BR, columns x0-1 .. x0+SW of each item of the pass (zeros outside the image),
+    // 4 loads in flight per thread (rolled: unrolled, every chunk's addresses stay in registers across the
+    // item loop)
+#pragma unroll 1
+    for (int k0 = 0; k0 < G::IPP * G::NPT4; k0 += 4) {
+      const int u = k0 / G::NPT4, ku = k0 % G::NPT4;
+      if (base + u >= i1) break;  // (an odd last pass: one item)
+      bf16* stile = (bf16*)lds_cw + u * G::TILEE;
+      int n, y0, x0;
+      strip_item<BR, SW>(base + u, nb, ns, n, y0, x0);
+      uint4 v[4];
+      unsigned pm[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = tid + G::NTH * (ku + k);
+        const int r = i / (TW * C8), rem = i % (TW * C8), col = rem / C8, c8 = rem % C8;
+        const int gy = y0 - 1 + r, gx = x0 - 1 + col;
+        v[k] = make_uint4(0u, 0u, 0u, 0u);
+        pm[k] = 0u;
+        if (i < G::NCH && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) {
+          const long e = (((long)n * H + gy) * W + gx) * C + 8 * c8;
+          v[k] = *(const uint4*)(xin + e);
+          if (MODE == B_EULER) pm[k] = dmask[e >> 3];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = tid + G::NTH * (ku + k);
+        const int r = i / (TW * C8), rem = i % (TW * C8), col = rem / C8, c8 = rem % C8;
+        if (i < G::NCH) *(uint4*)(stile + (r * TW + col) * PS + 8 * c8) = MODE == B_EULER ? mask8_bf16(v[k], pm[k]) : v[k];
+      }
+    }
+    __syncthreads();
+    const long item = base + ph;
+    if (item >= i1) continue;  // (wave-uniform; the next pass begins with the barrier)
+    int n, y0, x0;
+    strip_item<BR, SW>(item, nb, ns, n, y0, x0);
+    f32x4 acc[2][NTW];
+#pragma unroll
+    for (int o = 0; o < 2; ++o)
+#pragma unroll
+      for (int j = 0; j < NTW; ++j) acc[o][j] = bz[o];
+    bf16x8 Aa[KQ][2], Ab[KQ][2];
+    auto load_a = [&](bf16x8(&A)[KQ][2], int q) {
+#pragma unroll
+      for (int s = 0; s < KQ; ++s)
+#pragma unroll
+        for (int o = 0; o < 2; ++o) A[s][o] = *(const bf16x8*)(wl + ((long)o * KS + KQ * q + s) * 512);
+    };
+    // chunk q: k-steps KQ q .. KQ q + KQ - 1 = tap t, channels c0 + 32 s + 8 g .. + 7 of the pixel shifted by t
+    auto mac = [&](const bf16x8(&A)[KQ][2], int q) {
+      const int t = q / G::QT, c0 = (q % G::QT) * (32 * KQ);
+      const int off = ((t / 3) * TW + t % 3) * PS + c0;
+#pragma unroll
+      for (int s = 0; s < KQ; ++s)
+#pragma unroll
+        for (int j = 0; j < NTW; ++j) {
+          const uint4 bv = *(const uint4*)(tile + tb[j] + off + 32 * s);
+#pragma unroll
+          for (int o = 0; o < 2; ++o)
+            acc[o][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[s][o], __builtin_bit_cast(bf16x8, bv), acc[o][j], 0, 0, 0);
+        }
+    };
+    load_a(Aa, 0);
+#pragma unroll 1
+    for (int q = 0; q < NQ; q += 2) {
+      if (q + 1 < NQ) load_a(Ab, q + 1);
+      mac(Aa, q);
+      if (q + 2 < NQ) load_a(Aa, q + 2);
+      if (q + 1 < NQ) mac(Ab, q + 1);
+    }
+    mfma_bf16_settle();  // (the epilogue branches: every path must see the result's wait states)
+#pragma unroll
+    for (int o = 0; o < 2; ++o)
+#pragma unroll
+      for (int j = 0; j < NTW; ++j) {
+        const int ot = ot0 + o, r = trow[j], px = tpx[j];
+        const bool ok = y0 + r < H && (!STRIP || x0 + px < W);  // (rows past the image; a 16-column last strip)
+        const long pix = ((long)n * H + y0 + r) * W + x0 + px;
+        const long oi = pix * C + 16 * ot + 4 * g;  // this lane's 4 channels
+        const uint2 cw = *(const uint2*)(tile + ((r + 1) * TW + px + 1) * PS + 16 * ot + 4 * g);  // x or dz at the pixel
+        const float ctr[4] = {__uint_as_float(cw.x << 16), __uint_as_float(cw.x & 0xffff0000u),
+                              __uint_as_float(cw.y << 16), __uint_as_float(cw.y & 0xffff0000u)};
+        const f32x4 a = acc[o][j];
+        float v[4];
+        if constexpr (MODE == F_EULER) {
+          unsigned nib = 0;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            nib |= (a[e] > 0.f ? 1u : 0u) << e;
+            v[e] = fmaf(h, fmaxf(a[e], 0.f), ctr[e]);
+          }
+          if (mask) {  // the pixel's 16 channels of this o-tile: 4 nibbles, one 16-bit store
+            unsigned m = nib << (4 * g);
+            m |= (unsigned)__shfl_xor((int)m, 16, 64);
+            m |= (unsigned)__shfl_xor((int)m, 32, 64);
+            if (g == 0 && ok) *(uint16_t*)(mask + (pix * C + 16 * ot) / 8) = (uint16_t)m;
+          }
+        } else if constexpr (MODE == F_CONV) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = a[e];
+        } else if constexpr (MODE == B_CONV) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = fmaf(two_gamma, ctr[e], -a[e]);
+        } else {  // B_EULER: the tile holds dz = dy & mask, dy itself from global memory
+          uint2 dw = make_uint2(0u, 0u);
+          if (ok) dw = *(const uint2*)(xin + oi);
+          const float d0[4] = {__uint_as_float(dw.x << 16), __uint_as_float(dw.x & 0xffff0000u),
+                               __uint_as_float(dw.y << 16), __uint_as_float(dw.y & 0xffff0000u)};
+          const float hg = h * two_gamma;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = fmaf(hg, ctr[e], fmaf(-h, a[e], d0[e]));
+        }
+        if (ok) *(uint2*)(out + oi) = make_uint2(pk_bf16_rn(v[0], v[1]), pk_bf16_rn(v[2], v[3]));
+      }
+  }
+}
+
+// W: the image width (= SW unless STRIP)
+template <int C, int SW, bool STRIP, int MODE>
+static int launch_convbw(const bf16* xin, bf16* out, uint8_t* mask, const bf16* w, const float* bias, float h,
+                         float two_gamma, int N, int H, int W, const uint8_t* dmask, hipStream_t s) {
+  using G = BfWide<C, SW>;
+  constexpr size_t lds = G::LDS;
+  if (lds > 64 * 1024) {  // above the default dynamic-LDS limit: raised once per instantiation and device
+    static bool raised[64];
+    int dev = 0;
+    ASR_TRY(hip_check(hipGetDevice(&dev), "hipGetDevice"));
+    if (dev < 0 || dev >= 64 || !raised[dev]) {
+      ASR_TRY(hip_check(hipFuncSetAttribute((const void*)k_convbw<C, SW, STRIP, MODE>,
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                        "hipFuncSetAttribute"));
+      if (dev >= 0 && dev < 64) raised[dev] = true;
+    }
+  }
+  const long items = STRIP ? strip_items(N, H, W) : (long)N * ((H + 3) / 4);
+  const long passes = (items + G::IPP - 1) / G::IPP;  // (a pass: IPP items under one read of the pack)
+  const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, 160 * 1024 / lds));  // persistent workgroups per CU
+  const long grid = std::max<long>(1, std::min<long>(passes, (long)per_cu * launch_cus()));
+  hipLaunchKernelGGL((k_convbw<C, SW, STRIP, MODE>), dim3((unsigned)grid), dim3(G::NTH), lds, s, xin, out, mask, w, bias,
+                     h, two_gamma, N, H, W, dmask);
+  ASR_LAUNCH_CHECK("k_convbw");
+  return ASR_OK;
+}
+
+// k_wgradb's C = 64 workgroup on channel blocks (ib, ob) of an image CT channels deep.  An item is 128 pixels
+// as there; the workgroup's share of the items is blockIdx.x of gridDim.x, its slab row blockIdx.x.
+template <int CT, int SW, bool STRIP, bool MASKED>
+__global__ __launch_bounds__((WgB<64, SW>::NTH)) void k_wgradbw(const bf16* __restrict__ x, const bf16* __restrict__ dy,
+                                                               const uint8_t* __restrict__ dmask, int N, int H, float h,
+                                                               int Wimg, float* __restrict__ slabs) {
+  constexpr int C = 64, NB = CT / C;
+  using G = WgB<C, SW>;
+  static_assert(!STRIP || SW == kStripW, "a band x strip item is 4 x 32 pixels");
+  static_assert(G::PS == 1 && G::NO == 2, "k_wgradbw: the C = 64 wave layout");
+  const int W = STRIP ? Wimg : SW;
+  const int ib = blockIdx.y / NB, obk = blockIdx.y % NB;  // the input- and output-channel blocks
+  constexpr int TW = G::TW, BR = G::BR, NO = G::NO, OT = G::OT;
+  constexpr long E = 9L * CT * CT;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_ww[];
+  bf16* xt = (bf16*)lds_ww;  // [BR+2][TW][64] (chunk-swizzled per pixel)
+  bf16* dzt = xt + G::XE;    // [BR][SW][64]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, lx = lane & 15;
+  const int q = lx >> 2, pq = lx & 3;
+  const int it = wave / (OT / NO), ob = (wave % (OT / NO)) * NO;
+  const int nb = (H + BR - 1) / BR, ns = STRIP ? (W + SW - 1) / SW : 1;
+  const long items = (long)N * nb * ns;
+  const long i0 = (long)blockIdx.x * items / gridDim.x, i1 = (long)(blockIdx.x + 1) * items / gridDim.x;
+  f32x4 acc[9][NO], accb[NO];
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int o = 0; o < NO; ++o) acc[t][o] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int o = 0; o < NO; ++o) accb[o] = f32x4{0.f, 0.f, 0.f, 0.f};
+  uint4 px[G::XPT], pd[G::DPT];
+  unsigned pm[G::DPT];  // the relu bits, applied at the LDS store
+  auto fetch = [&](long item) {
+    int n, y0, x0;
+    strip_item<BR, SW>(item, nb, ns, n, y0, x0);
+#pragma unroll
+    for (int k = 0; k < G::XPT; ++k) {
+      const int i = tid + k * G::NTH;
+      px[k] = make_uint4(0u, 0u, 0u, 0u);
+      const int r = i / (TW * G::C8), rem = i % (TW * G::C8), col = rem / G::C8, c8 = rem % G::C8;
+      const int gy = y0 - 1 + r, gx = x0 - 1 + col;  // (halo columns: the neighbouring strips' pixels)
+      if (i < G::XCH && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W)
+        px[k] = *(const uint4*)(x + (((long)n * H + gy) * W + gx) * CT + C * ib + 8 * c8);
+    }
+#pragma unroll
+    for (int k = 0; k < G::DPT; ++k) {
+      const int i = tid + k * G::NTH;
+      pd[k] = make_uint4(0u, 0u, 0u, 0u);
+      pm[k] = 0u;
+      const int P = i / G::C8, c8 = i % G::C8, r = P / SW, c = P % SW;
+      // (rows past the image and, in a 16-column last strip, columns past it: zeros)
+      if (i < G::DCH && y0 + r < H && (!STRIP || x0 + c < W)) {
+        const long e = (((long)n * H + y0 + r) * W + x0 + c) * CT + C * obk + 8 * c8;
+        pd[k] = *(const uint4*)(dy + e);
+        if constexpr (MASKED) pm[k] = dmask[e >> 3];
+      }
+    }
+  };
+  auto store = [&]() {
+#pragma unroll
+    for (int k = 0; k < G::XPT; ++k) {
+      const int i = tid + k * G::NTH;
+      const int P = i / G::C8, c8 = i % G::C8;
+      if (i < G::XCH) *(uint4*)(xt + P * C + 8 * (c8 ^ G::swz(P))) = px[k];
+    }
+#pragma unroll
+    for (int k = 0; k < G::DPT; ++k) {
+      const int i = tid + k * G::NTH;
+      const int P = i / G::C8, c8 = i % G::C8;
+      if (i < G::DCH) *(uint4*)(dzt + P * C + 8 * (c8 ^ G::swz(P))) = MASKED ? mask8_bf16(pd[k], pm[k]) : pd[k];
+    }
+  };
+  // the lane's 8-B piece of channels 16 ch + 4 pq .. +3 at pixel P of a tile
+  auto piece = [&](const bf16* tile, int P, int ch) {
+    const int c16 = 2 * ch + (pq >> 1);
+    return tile + P * C + 8 * (c16 ^ G::swz(P)) + 4 * (pq & 1);
+  };
+  typedef short s16x8 __attribute__((ext_vector_type(8)));
+  auto frag = [&](const bf16* tile, int P1, int P2, int ch) {
+    const s16x4 a = tr4(piece(tile, P1, ch)), b = tr4(piece(tile, P2, ch));
+    const s16x8 c = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+    return __builtin_bit_cast(bf16x8, c);
+  };
+  bf16x8 ones;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ones[j] = (bf16)1.f;
+  if (i0 < i1) fetch(i0);
+  for (long item = i0; item < i1; ++item) {
+    const int y0 = (int)((item / ns) % nb) * BR;
+    const int rows = min(BR, H - y0), nch = STRIP ? rows : (rows * SW + 31) / 32;  // (32-pixel chunks: a strip's rows)
+    __syncthreads();  // the previous item's operands consumed
+    store();
+    __syncthreads();
+    if (item + 1 < i1) fetch(item + 1);  // in flight during this item's MFMAs
+    for (int ch = 0; ch < nch; ++ch) {  // (wave-uniform: EXEC stays full for the transposed reads)
+      const int k1 = 32 * ch + 4 * g + q, k2 = k1 + 16;
+      const int r1 = k1 / SW, c1 = k1 % SW, r2 = k2 / SW, c2 = k2 % SW;
+      bf16x8 B[NO];
+#pragma unroll
+      for (int o = 0; o < NO; ++o) B[o] = frag(dzt, r1 * SW + c1, r2 * SW + c2, ob + o);
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        const int d = (t / 3) * TW + t % 3;
+        const bf16x8 A = frag(xt, r1 * TW + c1 + d, r2 * TW + c2 + d, it);
+#pragma unroll
+        for (int o = 0; o < NO; ++o) acc[t][o] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B[o], acc[t][o], 0, 0, 0);
+      }
+      if (ib == 0 && it == 0) {  // (db once per o-block: the ib = 0 workgroups)
+#pragma unroll
+        for (int o = 0; o < NO; ++o) accb[o] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, B[o], accb[o], 0, 0, 0);
+      }
+    }
+  }
+  float* slab = slabs + (long)blockIdx.x * (E + CT);
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int o = 0; o < NO; ++o)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        slab[((long)t * CT + C * ib + 16 * it + 4 * g + e) * CT + C * obk + 16 * (ob + o) + lx] = h * acc[t][o][e];
+  if (ib == 0 && it == 0 && g == 0) {
+#pragma unroll
+    for (int o = 0; o < NO; ++o) slab[E + C * obk + 16 * (ob + o) + lx] = h * accb[o][0];
+  }
+}
+
+// k_wgradbw's pixel splits = its slab rows (launcher and every workspace): at least 8 items (1024 pixels) a
+// workgroup, two workgroups per CU over the (C/64)^2 channel-block pairs, at most 48 MB of slabs
+static int wgrad_wide_rows(int N, int H, int W, int C) {
+  const long items = strip_width(W) ? strip_items(N, H, W) : (long)N * ((H + 128 / W - 1) / (128 / W));
+  const long nblk = (long)(C / 64) * (C / 64), cap = 48000000L / ((9L * C * C + C) * 4);
+  return (int)std::max<long>(1, std::min<long>({(items + 7) / 8, std::max<long>(1, 2L * launch_cus() / nblk), cap}));
+}
+
+template <int C, int SW, bool STRIP, bool MASKED>
+static int launch_wgradbw(const bf16* x, const bf16* dy, const uint8_t* mask, int N, int H, int W, float h,
+                          float* slabs, int* nslabs, hipStream_t s) {
+  using G = WgB<64, SW>;
+  const int rows = wgrad_wide_rows(N, H, W, C);
+  hipLaunchKernelGGL((k_wgradbw<C, SW, STRIP, MASKED>), dim3(rows, (C / 64) * (C / 64)), dim3(G::NTH), G::LDS, s, x, dy,
+                     mask, N, H, h, W, slabs);
+  ASR_LAUNCH_CHECK("k_wgradbw");
+  *nslabs = rows;
+  return ASR_OK;
 }
 
 // The any-width kernels' instantiation for (C, W): f(C, SW, STRIP) as integral constants, the tile width and
@@ -1158,6 +1532,8 @@ static int dispatch_c_sw(const char* what, int C, int W, F&& f) {
     case 16: return at_c(std::integral_constant<int, 16>{});
     case 32: return at_c(std::integral_constant<int, 32>{});
     case 64: return at_c(std::integral_constant<int, 64>{});
+    case 128: return at_c(std::integral_constant<int, 128>{});
+    case 256: return at_c(std::integral_constant<int, 256>{});
   }
   return fail(ASR_E_UNSUPPORTED, "%s: C=%d W=%d", what, C, W);
 }
@@ -1169,11 +1545,19 @@ int convb_forward(const void* x, void* y, uint8_t* mask, const void* w, const fl
   return dispatch_c_sw("conv bf16 (any width)", C, W, [&](auto c, auto sw, auto strip) -> int {
     constexpr int CC = decltype(c)::value, SW = decltype(sw)::value;
     constexpr bool ST = decltype(strip)::value;
-    if (conv_only)
-      return launch_convb<CC, SW, ST, F_CONV>((const bf16*)x, (bf16*)y, nullptr, (const bf16*)w, bias, 1.f, 0.f, N, H,
-                                              W, nullptr, s);
-    return launch_convb<CC, SW, ST, F_EULER>((const bf16*)x, (bf16*)y, mask, (const bf16*)w, bias, h, 0.f, N, H, W,
-                                             nullptr, s);
+    if constexpr (CC >= 128) {  // W streamed from the pack
+      if (conv_only)
+        return launch_convbw<CC, SW, ST, F_CONV>((const bf16*)x, (bf16*)y, nullptr, (const bf16*)w, bias, 1.f, 0.f, N,
+                                                 H, W, nullptr, s);
+      return launch_convbw<CC, SW, ST, F_EULER>((const bf16*)x, (bf16*)y, mask, (const bf16*)w, bias, h, 0.f, N, H, W,
+                                                nullptr, s);
+    } else {
+      if (conv_only)
+        return launch_convb<CC, SW, ST, F_CONV>((const bf16*)x, (bf16*)y, nullptr, (const bf16*)w, bias, 1.f, 0.f, N, H,
+                                                W, nullptr, s);
+      return launch_convb<CC, SW, ST, F_EULER>((const bf16*)x, (bf16*)y, mask, (const bf16*)w, bias, h, 0.f, N, H, W,
+                                               nullptr, s);
+    }
   });
 }
 
@@ -1190,18 +1574,34 @@ int convb_backward(const void* dy, const uint8_t* mask, const void* x, const voi
   return dispatch_c_sw("conv bf16 backward (any width)", C, W, [&](auto c, auto sw, auto strip) -> int {
     constexpr int CC = decltype(c)::value, SW = decltype(sw)::value;
     constexpr bool ST = decltype(strip)::value;
-    if (dx) {
+    if constexpr (CC >= 128) {  // W streamed from the pack; the weight gradient over channel blocks
+      if (dx) {
+        if (conv_only)
+          ASR_TRY((launch_convbw<CC, SW, ST, B_CONV>((const bf16*)dy, (bf16*)dx, nullptr, (const bf16*)w, nullptr, 1.f,
+                                                     two_gamma, N, H, W, nullptr, s)));
+        else
+          ASR_TRY((launch_convbw<CC, SW, ST, B_EULER>((const bf16*)dy, (bf16*)dx, nullptr, (const bf16*)w, nullptr, h,
+                                                      two_gamma, N, H, W, mask, s)));
+      }
+      if (!need_w) return ASR_OK;
       if (conv_only)
-        ASR_TRY((launch_convb<CC, SW, ST, B_CONV>((const bf16*)dy, (bf16*)dx, nullptr, (const bf16*)w, nullptr, 1.f,
-                                                  two_gamma, N, H, W, nullptr, s)));
-      else
-        ASR_TRY((launch_convb<CC, SW, ST, B_EULER>((const bf16*)dy, (bf16*)dx, nullptr, (const bf16*)w, nullptr, h,
-                                                   two_gamma, N, H, W, mask, s)));
+        return launch_wgradbw<CC, SW, ST, false>((const bf16*)x, (const bf16*)dy, nullptr, N, H, W, 1.f, slabs, nslabs,
+                                                 s);
+      return launch_wgradbw<CC, SW, ST, true>((const bf16*)x, (const bf16*)dy, mask, N, H, W, h, slabs, nslabs, s);
+    } else {
+      if (dx) {
+        if (conv_only)
+          ASR_TRY((launch_convb<CC, SW, ST, B_CONV>((const bf16*)dy, (bf16*)dx, nullptr, (const bf16*)w, nullptr, 1.f,
+                                                    two_gamma, N, H, W, nullptr, s)));
+        else
+          ASR_TRY((launch_convb<CC, SW, ST, B_EULER>((const bf16*)dy, (bf16*)dx, nullptr, (const bf16*)w, nullptr, h,
+                                                     two_gamma, N, H, W, mask, s)));
+      }
+      if (!need_w) return ASR_OK;
+      if (conv_only)
+        return launch_wgradb<CC, SW, ST, false>((const bf16*)x, (const bf16*)dy, nullptr, N, H, W, 1.f, slabs, nslabs, s);
+      return launch_wgradb<CC, SW, ST, true>((const bf16*)x, (const bf16*)dy, mask, N, H, W, h, slabs, nslabs, s);
     }
-    if (!need_w) return ASR_OK;
-    if (conv_only)
-      return launch_wgradb<CC, SW, ST, false>((const bf16*)x, (const bf16*)dy, nullptr, N, H, W, 1.f, slabs, nslabs, s);
-    return launch_wgradb<CC, SW, ST, true>((const bf16*)x, (const bf16*)dy, mask, N, H, W, h, slabs, nslabs, s);
   });
 }
 

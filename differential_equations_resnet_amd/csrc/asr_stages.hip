@@ -1031,8 +1031,8 @@ int stages_check(const asr_stages_config* c) {
       if (s > 0 && c->stride[s]) H = (H + c->stride[s] - 1) / c->stride[s], W = (W + c->stride[s] - 1) / c->stride[s];
       if (c->L[s] > 0 && !convb_supported(W, c->C[s]))
         return fail(ASR_E_UNSUPPORTED,
-                    "asr_stages: bf16 stage %d needs C in {16, 32, 64} and W == 8 or W %% 16 == 0 (C=%d W=%d)", s, c->C[s],
-                    W);
+                    "asr_stages: bf16 stage %d needs C in {16, 32, 64, 128, 256} and W == 8 or W %% 16 == 0 "
+                    "(C=%d W=%d)", s, c->C[s], W);
       if (c->C[s] % 8) return fail(ASR_E_UNSUPPORTED, "asr_stages: bf16 stage %d: C=%d not a multiple of 8", s, c->C[s]);
     }
   }
@@ -1126,7 +1126,9 @@ SLayout stages_layout(const asr_stages_config* c) {
     g.grp = ws.take((size_t)std::max(g.L, 1) * g.grp_stride * 4);
     g.slab_stride = (long)g.slab_rows * (g.E + g.C);
     g.slabs = ws.take(g.fused == kFusedDeep16 ? deep16_slab_bytes(c->N, g.L) : (size_t)g.L * g.slab_stride * 4);
-    if (g.L > 0) L.cws_bytes = std::max(L.cws_bytes, asr_conv_backward_workspace_bytes(c->N, g.H, g.W, g.C, ASR_F32));
+    // (the fp32 blocks' dz scratch; a bf16 stage at C > 64 never runs them, and their 512 slab rows are GBs there)
+    if (g.L > 0 && !(L.bf && g.C > 64))
+      L.cws_bytes = std::max(L.cws_bytes, asr_conv_backward_workspace_bytes(c->N, g.H, g.W, g.C, ASR_F32));
     if (g.S) L.tws_bytes = std::max(L.tws_bytes, trans_ws_bytes(c->N, g.Hp, g.Wp, g.Cp, g.C, g.S));
   }
   const int K = c->num_classes;

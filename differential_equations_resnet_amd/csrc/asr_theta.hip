@@ -644,7 +644,7 @@ using namespace asr;
 extern "C" {
 
 const char* asr_last_error(void) { return g_err; }
-int asr_abi_version(void) { return 11; }
+int asr_abi_version(void) { return 12; }
 
 int asr_device_cu_count(void) { return cu_count(); }
 

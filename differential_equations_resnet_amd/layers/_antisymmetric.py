@@ -138,7 +138,9 @@ class AntisymmetricConvBase(Layer):
 
     def call_device(self, x, **kwargs):
         """output = conv2d(x, W(theta), SAME, stride 1) + bias on a device NHWC
-        tensor (float32 or bfloat16), i.e. the layer's call() (…3By3.py:157-171)."""
+        tensor (float32 or bfloat16), i.e. the layer's call() (…3By3.py:157-171).
+        bfloat16 at kernel_size 3 takes C in {16, 32, 64, 128, 256} and W == 8 or a
+        multiple of 16 (asr_conv_forward's set; W rounded to nearest above C = 64)."""
         torch = _torch()
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise TypeError(f"{self.name}: eager calls take a device (HIP) tensor; use a Model for host arrays")

@@ -22,9 +22,10 @@ All blocks share one kernel size; conv1's is free of it (the reference's
 builder passes its kernel_size to conv1 and, with kernel_type='regular', to
 every block conv; its antisymmetric blocks are the 3by3 layer).  Blocks of
 size 5 / 7 run in float32 at any shape and in bfloat16 at C in {16, 32, 64},
-W in {8, 16, 32}; 3 x 3 Euler blocks run in bfloat16 at C in {16, 32, 64} and
-W == 8 or any multiple of 16 (column-strip kernels from W = 48 on), RK2 blocks
-at W == 32 (asr_net_config's accepted set; the executor refuses the rest).
+W in {8, 16, 32}; 3 x 3 Euler blocks run in bfloat16 at C in {16, 32, 64, 128,
+256} and W == 8 or any multiple of 16 (column-strip kernels from W = 48 on;
+at C >= 128 W is streamed from its pack and rounded to nearest), RK2 blocks
+at W == 32 and C <= 64 (asr_net_config's accepted set; the executor refuses the rest).
 
 With num_stages > 2 (e.g. the He-style ResNet-32, blocks [10, 10, 10] at
 32^2 x 16, 16^2 x 32, 8^2 x 64; tfkeras_resnets.py:575-593) a stage whose
@@ -127,12 +128,12 @@ class StagesPlan:
 
     def stages_bf16_ok(self):
         """Whether the bf16 block kernels take every stage with blocks (C in
-        {16, 32, 64}, W == 8 or a multiple of 16; asr_stages_config.dtype)."""
+        {16, 32, 64, 128, 256}, W == 8 or a multiple of 16; asr_stages_config.dtype)."""
         W = self.W
         for C, L, S in self.stages:
             if S:
                 W = (W + S - 1) // S
-            if L > 0 and (C not in (16, 32, 64) or not (W == 8 or (W >= 16 and W % 16 == 0))):
+            if L > 0 and (C not in (16, 32, 64, 128, 256) or not (W == 8 or (W >= 16 and W % 16 == 0))):
                 return False
             if C % 8:
                 return False
@@ -416,7 +417,7 @@ class NativeModel:
                 return "bfloat16"
             if not self._warned_stages_dtype:
                 warnings.warn(f"this multi-stage net runs in float32 on the native executor (dtype={dtype!r} "
-                              "requested: bf16 needs C in {16, 32, 64} and W == 8 or W % 16 == 0 at every stage "
+                              "requested: bf16 needs C in {16, 32, 64, 128, 256} and W == 8 or W % 16 == 0 at every stage "
                               "with blocks)", stacklevel=3)
                 self._warned_stages_dtype = True
             return "float32"

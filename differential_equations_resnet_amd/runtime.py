@@ -460,9 +460,10 @@ class NetExecutor:
     (Conv2DAntisymmetric(kernel_size)) or ASR_PARAM_REGULAR, Euler blocks,
     float32 at any shape and bfloat16 at C in {16, 32, 64}, W in {8, 16, 32};
     such a network runs one launch per block.  conv1's size is free of the
-    blocks'.  kernel_size 3 in bfloat16 takes C in {16, 32, 64} and W == 8 or
-    any multiple of 16 (Euler blocks; RK2 at W == 32): off W == 32 the blocks
-    run one launch each, from W = 48 on the column-strip kernels.  Anything
+    blocks'.  kernel_size 3 in bfloat16 takes C in {16, 32, 64, 128, 256} and
+    W == 8 or any multiple of 16 (Euler blocks; RK2 at W == 32 and C <= 64):
+    off W == 32, and at C >= 128, the blocks run one launch each, from W = 48
+    on the column-strip kernels.  Anything
     else raises AsrUnsupported (or ValueError for an even
     size) with the accepted set in the message, before any launch."""
 
@@ -588,7 +589,7 @@ class StagesExecutor:
     (single_layer_conv_block) and its identity Euler blocks, head.  float32
     (the reference's precision) or bfloat16 (the identity blocks' activations
     and convs in bf16 with fp32 accumulation; stem, transitions, head and every
-    weight gradient in fp32; stages with blocks need C in {16, 32, 64} and
+    weight gradient in fp32; stages with blocks need C in {16, 32, 64, 128, 256} and
     W == 8 or a multiple of 16).  Parameters / gradients are flat float32 buffers in the
     asr_stages_config order; same call surface as NetExecutor."""
 

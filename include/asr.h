@@ -143,10 +143,18 @@ int asr_theta_to_w(const float* theta, long theta_stride, int L, int C, const in
  *   bias: C floats or NULL;  mask: asr_mask_bytes(N,H,W,C) bytes, relu bit of
  *   element (pixel, o) at bit index pixel*C + o (NHWC bit order, LSB first).
  * float32 takes any shape.  bfloat16 (forward, backward and the stack calls
- * below) takes C in {16, 32, 64} and W == 8 or W a multiple of 16 (the MFMA
- * tile is 16 pixels of one row), any H: k_convb / k_wgradb over whole rows at
- * W in {32, 16, 8}, over column strips of 32 pixels from W = 48 on; any other
- * bf16 shape is ASR_E_UNSUPPORTED before any launch.
+ * below) takes C in {16, 32, 64, 128, 256} (ABI 12: 128 and 256) and W == 8 or
+ * W a multiple of 16 (the MFMA tile is 16 pixels of one row), any H: k_convb /
+ * k_wgradb over whole rows at W in {32, 16, 8}, over column strips of 32
+ * pixels from W = 48 on; at C in {128, 256} the same items on k_convbw (W
+ * streamed from its pack) and k_wgradbw (the weight gradient over 64 x 64
+ * channel blocks).  Any other bf16 shape is ASR_E_UNSUPPORTED before any
+ * launch.  asr_theta_to_w's bf16 pack rounds W to nearest above C = 64 (the
+ * balanced rounding is C <= 64): an antisymmetric W stays exactly
+ * antisymmetric, and deep stacks at C >= 128 carry the per-channel offset of
+ * nearest rounding that ASR_VARIANT_W_BF16 describes (not measured at these
+ * widths).  asr_conv_backward_workspace_bytes stays <= 64 MB at C >= 128 for
+ * every N, H, W (the weight gradient writes at most 48 MB of slabs).
  * Replaces Conv2DAntisymmetric3By3.call (…3By3.py:157-171) and
  * single_layer_identity_block's relu/scale/add (tfkeras_resnets.py:89-92). */
 int asr_conv_forward(int mode, const void* x, void* y, uint8_t* mask, const void* w,
@@ -180,7 +188,8 @@ long asr_mask_bytes(int N, int H, int W, int C);
  * runs).  On that path the strides must keep every layer's vector accesses
  * aligned, else ASR_E_ARG before any launch: y_stride % 4, mask_stride % 2,
  * bias_stride % 4 and, in bf16, w_stride % 8.  Other shapes (bf16: C in
- * {16,32,64}, W == 8 or W % 16 == 0) run the per-block kernels in sequence. */
+ * {16,32,64,128,256}, W == 8 or W % 16 == 0) run the per-block kernels in
+ * sequence. */
 int asr_block_stack_forward(const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride,
                             const void* w, long w_stride, const float* bias, long bias_stride, float h,
                             int N, int H, int W, int C, int L, int dtype, int store_all, asr_stream_t stream);
@@ -358,14 +367,15 @@ typedef struct asr_net_config {
  *     ASR_PARAM_REGULAR (Conv2DAntisymmetric(kernel_size), a regular Conv2D);
  *   - bfloat16, kernel_size in {5, 7}: the set of asr_conv_forward_k_bf16,
  *     C in {16, 32, 64} and W in {8, 16, 32}, any H;
- *   - bfloat16, kernel_size 3: C in {16, 32, 64} and W == 8 or W % 16 == 0
- *     (asr_conv_forward's bf16 set), for any conv1_kernel_size.  W == 32 runs
- *     what it ran before; any other width runs one launch per block, forward
+ *   - bfloat16, kernel_size 3: C in {16, 32, 64, 128, 256} and W == 8 or
+ *     W % 16 == 0 (asr_conv_forward's bf16 set), for any conv1_kernel_size.
+ *     W == 32 at C <= 64 runs what it ran before; any other width, and every
+ *     width at C in {128, 256}, runs one launch per block, forward
  *     and backward (Euler blocks only), conv1 on the VALU / generic arms and
  *     the variant bits PER_BLOCK_*, NO_FOLD, FULL_DXL, FULL_SLABS have no
  *     effect there;
  *   - ASR_INTEGRATOR_RK2 needs kernel_size 3 (any conv1_kernel_size) and, in
- *     bfloat16, W == 32;
+ *     bfloat16, W == 32 and C in {16, 32, 64};
  *   - ASR_VARIANT_INFERENCE works for every accepted config.
  * With both sizes 0 or 3 every call launches what it launched at ABI 9.
  * kernel_size != 3 runs one launch per block, forward and backward (the
@@ -520,7 +530,7 @@ typedef struct asr_stages_config {
  * [C[s]]); fc kernel [C_last, K], bias [K]. */
 /* ASR_OK, or the code (and asr_last_error) the calls below fail with for this
  * config: ASR_E_ARG for a malformed one, ASR_E_UNSUPPORTED for a shape the
- * kernels do not take (e.g. a bf16 stage with blocks outside C {16,32,64} x
+ * kernels do not take (e.g. a bf16 stage with blocks outside C {16,32,64,128,256} x
  * {W == 8 or W % 16 == 0}: asr_conv_forward's bf16 set; such stages run one
  * launch per block off the fused stage shapes).
  * ABI 8.  Host only. */
