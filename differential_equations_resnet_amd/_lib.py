@@ -93,6 +93,16 @@ class AugPlanConfig(ct.Structure):
                 ("pad_top", ct.c_int), ("pad_left", ct.c_int), ("flip_src", ct.c_int), ("color", ct.c_int * 2)]
 
 
+ASR_OPT_SGD, ASR_OPT_ADAM, ASR_OPT_RMSPROP = 0, 1, 2
+ASR_OPT_NESTEROV, ASR_OPT_AMSGRAD = 1, 2
+
+
+class OptimizerConfig(ct.Structure):
+    """asr_optimizer_config (include/asr.h)."""
+    _fields_ = [("kind", ct.c_int), ("flags", ct.c_int), ("lr", ct.c_float), ("a", ct.c_float), ("b", ct.c_float),
+                ("eps", ct.c_float), ("step", ct.c_long), ("grad_scale", ct.c_float)]
+
+
 _P = ct.c_void_p
 _I = ct.c_int
 _L = ct.c_long
@@ -159,6 +169,8 @@ SIGNATURES = [
     ("asr_stages_forward", _I, [ct.POINTER(StagesConfig), _P, _P, _P, _P, _S, _P]),
     ("asr_stages_forward_backward", _I, [ct.POINTER(StagesConfig), _P, _P, _P, _P, _P, _P, _P, _S, _P]),
     ("asr_adam_update", _I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _L, _F, _P]),
+    ("asr_optimizer_slots", _I, [_I, _I]),
+    ("asr_optimizer_update", _I, [ct.POINTER(OptimizerConfig), _P, _P, _P, _L, _P]),
     ("asr_segment_sq_norms", _I, [_P, _P, _I, _P, _P]),
     ("asr_batch_metrics", _I, [_P, _P, _P, _I, _I, _P, _P]),
     ("asr_augment_batch", _I, [_P, _L, ct.POINTER(AugPlanConfig), _P, _I, _P, _P]),

@@ -431,6 +431,7 @@ class Model:
         self.name = name or _unique_name("model")
         self.layers = self._topo_layers()
         self._native = None  # lowered executor cache (lowering.NativeModel)
+        self._compiled = None  # compile()'s record (keras_training)
 
     @property
     def input(self):
@@ -560,6 +561,46 @@ class Model:
         n = int(x.shape[0])
         bs = int(batch_size or min(n, 256))
         return self.compile_native(bs, dtype).predict(x)
+
+    # -- the Keras training calls (keras_training.py) ---------------------------
+    def compile(self, optimizer, loss="categorical_crossentropy", metrics=None, dtype=None):
+        """tf.keras Model.compile.  optimizer: an optimizers.SGD / Adam / RMSprop, 'sgd' | 'adam' |
+        'rmsprop', or a training.AdamOptimizer; loss: 'categorical_crossentropy' (the executor's);
+        metrics: None, [] or ['accuracy'] / ['acc']; dtype: the executor dtype, as Training's (None:
+        the plan's own).  Host only: nothing is lowered before the first step."""
+        from . import keras_training
+        keras_training.compile_model(self, optimizer, loss, metrics, dtype)
+
+    def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose=1, callbacks=None, validation_split=0.0,
+            validation_data=None, shuffle=True, class_weight=None, sample_weight=None, initial_epoch=0,
+            steps_per_epoch=None, validation_steps=None):
+        """tf.keras Model.fit on NHWC uint8 / float32 images and one-hot labels (numpy or torch), or on
+        a dataset of device batches with steps_per_epoch; returns a History.  callbacks,
+        validation_split, class_weight and sample_weight raise AsrUnsupported, as does a fit under
+        distributed.is_initialized() (data-parallel training runs through Training)."""
+        from . import keras_training
+        return keras_training.fit(self, x, y, batch_size, epochs, verbose, callbacks, validation_split,
+                                  validation_data, shuffle, class_weight, sample_weight, initial_epoch,
+                                  steps_per_epoch, validation_steps)
+
+    def evaluate(self, x=None, y=None, batch_size=None, verbose=1, steps=None):
+        """[loss, acc] (the scalar loss without metrics) on the forward-only executor."""
+        from . import keras_training
+        return keras_training.evaluate(self, x, y, batch_size, verbose, steps)
+
+    def train_on_batch(self, x, y):
+        """One update on one batch: its loss (and accuracy) from before the update."""
+        from . import keras_training
+        return keras_training.train_on_batch(self, x, y)
+
+    def test_on_batch(self, x, y):
+        from . import keras_training
+        return keras_training.test_on_batch(self, x, y)
+
+    @property
+    def optimizer(self):
+        c = getattr(self, "_compiled", None)
+        return None if c is None else c.optimizer
 
     def __call__(self, *args, **kwargs):
         raise TypeError("Model objects are executed with predict()/Training, not called as layers")

@@ -376,7 +376,8 @@ class NativeModel:
     """The device state of one Model lowered onto the native executor.
 
     ONE instance per Model owns the flat fp32 device parameters (Keras
-    order), the Adam moments and step, and every executor built for it,
+    order), the Adam moments and step (apply_adam) or the Keras optimiser's
+    state buffer (apply_optimizer), and every executor built for it,
     keyed by (batch size, activation dtype, input kind) — so a predict() at
     another batch size or dtype reads the trained parameters and a
     set_weights()/load_variables() reaches every executor.  Host-side
@@ -400,6 +401,8 @@ class NativeModel:
         self.m = None
         self.v = None
         self.step = 0
+        self.opt = None        # the optimizers.Optimizer whose state opt_state holds
+        self.opt_state = None  # [slots * n_params] float32, apply_optimizer
         self._host_stale = False
         self.push_weights()
 
@@ -500,12 +503,26 @@ class NativeModel:
         self._rt.adam_update(self.params, grads, self.m, self.v, lr, beta1, beta2, epsilon, self.step, grad_scale)
         self._host_stale = True
 
+    def apply_optimizer(self, opt, grads, lr=None, grad_scale=1.0):
+        """One update of the parameters by the optimizers.Optimizer `opt` (one launch,
+        asr_optimizer_update).  `lr` replaces opt.lr (a schedule's value; opt.decay still
+        applies).  The state buffer belongs to this NativeModel, so every batch-size view
+        shares it; it is allocated, zeroed, on first use and again when another optimiser
+        object arrives."""
+        if self.opt is not opt or self.opt_state is None:
+            self.opt_state = self._torch.zeros(opt.slots() * self.n_params, dtype=self._torch.float32,
+                                               device=self.device)
+            self.opt = opt
+        self._rt.optimizer_update(opt.next_config(lr, grad_scale), self.params, grads, self.opt_state)
+        opt.iterations += 1
+        self._host_stale = True
+
 
 class NativeView:
     """A NativeModel at a fixed batch size and dtype.  Everything else
     (parameters, Adam state, weight sync) is the shared NativeModel's."""
 
-    _SHARED = ("params", "m", "v", "step")
+    _SHARED = ("params", "m", "v", "step", "opt", "opt_state")
 
     def __init__(self, state: NativeModel, batch_size: int, dtype):
         object.__setattr__(self, "state", state)

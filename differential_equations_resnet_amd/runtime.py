@@ -22,7 +22,7 @@ __all__ = [
     "require_gpu", "dtype_code", "torch_dtype", "ParamMap", "param_map", "theta_count", "theta_to_w",
     "conv_forward", "block_stack_forward", "block_stack_backward", "conv_backward", "rk2_forward", "rk2_backward",
     "integrator_code", "NetExecutor", "adam_update", "stack_status", "transition_forward", "transition_backward",
-    "StagesExecutor", "augment_batch",
+    "StagesExecutor", "augment_batch", "optimizer_slots", "optimizer_update",
 ]
 
 
@@ -413,6 +413,29 @@ def rk2_stack_backward(dyL, x0, ys, xmids, masks1, masks2, w, pmap: ParamMap, h:
 def adam_update(params, grads, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
     _lib.call("asr_adam_update", _p(params), _p(grads), _p(m), _p(v), params.numel(), float(lr), float(beta1),
               float(beta2), float(eps), int(step), float(grad_scale), _stream())
+
+
+def optimizer_slots(kind: int, flags: int = 0) -> int:
+    """How many n-float state buffers the optimiser needs (asr_optimizer_slots, host only)."""
+    n = int(_lib.load().asr_optimizer_slots(int(kind), int(flags)))
+    if n < 0:
+        raise ValueError(f"optimizer kind {kind} does not take flags {flags}")
+    return n
+
+
+def optimizer_update(cfg, params, grads, state):
+    """One SGD / Adam / RMSprop update of the flat float32 `params` in one launch
+    (asr_optimizer_update).  cfg: _lib.OptimizerConfig (optimizers.Optimizer.next_config fills it);
+    state: the caller's zero-initialised float32 [slots * n] buffer."""
+    n = params.numel()
+    slots = optimizer_slots(cfg.kind, cfg.flags)
+    if grads.numel() != n or state.numel() != slots * n:
+        raise ValueError(f"optimizer_update: {n} params need {n} grads and {slots} x {n} state floats, got "
+                         f"{grads.numel()} and {state.numel()}")
+    for name, t in (("params", params), ("grads", grads), ("state", state)):
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"optimizer_update: {name} must be a contiguous float32 device tensor")
+    _lib.call("asr_optimizer_update", ct.byref(cfg), _p(params), _p(grads), _p(state), n, _stream())
 
 
 def augment_batch(features, plan, items, out=None):

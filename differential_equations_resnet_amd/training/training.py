@@ -5,7 +5,9 @@ instead of a TF1 Session.
 Semantics kept from the reference:
   * loss = mean Keras categorical cross-entropy on the softmax outputs
     (:290-296), regularisation losses ignored (the reference's TODO);
-  * tf.train.AdamOptimizer with the epsilon-hat update (:297-300);
+  * tf.train.AdamOptimizer with the epsilon-hat update (:297-300), or one of
+    optimizers.SGD / Adam / RMSprop (the notebooks' tf.keras.optimizers
+    alternative), applied by asr_optimizer_update;
   * streaming mean_loss / accuracy metrics, reset every epoch and before
     each evaluation (:316-354, :450-471);
   * per-layer gradient mean-norms ||g||_2 / size: for antisymmetric models
@@ -81,6 +83,9 @@ class Training:
         self._torch = torch
         self.model_build_function = model_build_function
         self.kernel_type = kernel_type
+        if optimizer is not None and not isinstance(optimizer, AdamOptimizer):
+            from .. import optimizers
+            optimizer = optimizers.get(optimizer)  # tf.keras.optimizers.SGD / Adam / RMSprop or their names
         self.optimizer = optimizer if optimizer is not None else AdamOptimizer(epsilon=1e-7)
         self.learning_rate_placeholder = learning_rate_placeholder
         self.train_dataset = train_dataset
@@ -245,8 +250,11 @@ class Training:
         distributed.allreduce_grads(grads)
         norms = self._gradient_mean_norms(grads) if with_norms else None
         opt = self.optimizer
-        self.native.apply_adam(grads, float(learning_rate), opt.beta1, opt.beta2, opt.epsilon,
-                               grad_scale=1.0 / self.world)
+        if isinstance(opt, AdamOptimizer):
+            self.native.apply_adam(grads, float(learning_rate), opt.beta1, opt.beta2, opt.epsilon,
+                                   grad_scale=1.0 / self.world)
+        else:  # the schedule's rate replaces opt.lr; opt.decay still applies to it
+            self.native.apply_optimizer(opt, grads, lr=float(learning_rate), grad_scale=1.0 / self.world)
         runtime.batch_metrics(probs, labels, loss, self._accum)
         self.g_step += 1
         self.variables_updated = True
@@ -368,8 +376,10 @@ class Training:
     def save(self, model_save_dir, saver, tags=["default"], name=None, include_global_step=True,
              include_last_training_loss=True, include_metrics=True, force_save=False):
         """Writes <dir>/<model name>/variables.npz (Keras-order weights +
-        Adam state) and state.json (global step, metrics) on rank 0; the
-        directory name follows the reference's pattern (:781-858)."""
+        the optimiser's state: adam_m / adam_v for an AdamOptimizer, optimizer_state
+        for an optimizers.* one, whose kind and iterations go to state.json) and
+        state.json (global step, metrics) on rank 0; the directory name follows
+        the reference's pattern (:781-858)."""
         if not self.variables_updated and not force_save:
             print("Abort: Nothing to save, no training has been performed since the model was last saved.")
             return None
@@ -399,29 +409,48 @@ class Training:
             if self.native.m is not None:
                 arrays["adam_m"] = self.native.m.cpu().numpy()
                 arrays["adam_v"] = self.native.v.cpu().numpy()
+            state = {"global_step": self.g_step, "adam_step": self.native.step, "saver": saver,
+                     "tags": list(tags), "metrics": dict(zip(self.metric_names, self.metric_values))}
+            if not isinstance(self.optimizer, AdamOptimizer):
+                if self.native.opt is self.optimizer and self.native.opt_state is not None:
+                    arrays["optimizer_state"] = self.native.opt_state.cpu().numpy()
+                state["optimizer"] = {"kind": type(self.optimizer).__name__, "flags": self.optimizer.flags,
+                                      "iterations": self.optimizer.iterations}
             np.savez(os.path.join(path, "variables.npz"), **arrays)
             with open(os.path.join(path, "state.json"), "w") as f:
-                json.dump({"global_step": self.g_step, "adam_step": self.native.step, "saver": saver,
-                           "tags": list(tags), "metrics": dict(zip(self.metric_names, self.metric_values))}, f)
+                json.dump(state, f)
         self.variables_updated = False
         return path
 
     def load_variables(self, path):
-        """Restore weights (+ Adam state when present) saved by save()."""
+        """Restore weights (+ the optimiser's state when present) saved by save()."""
         torch = self._torch
         d = path if os.path.isdir(path) else os.path.dirname(path)
+        st = os.path.join(d, "state.json")
+        s = {}
+        if os.path.exists(st):
+            with open(st) as f:
+                s = json.load(f)
+        saved = s.get("optimizer")
+        opt = self.optimizer
+        if saved is not None and (isinstance(opt, AdamOptimizer) or saved["kind"] != type(opt).__name__
+                                  or saved["flags"] != opt.flags):
+            raise ValueError(f"the checkpoint holds the state of a {saved['kind']} optimizer (flags "
+                             f"{saved['flags']}); this Training runs {type(opt).__name__}")
         with np.load(os.path.join(d, "variables.npz"), allow_pickle=False) as f:
             ws = [f[k] for k in sorted(k for k in f.files if k.startswith("w"))]
             self.model.set_weights(ws)
             if "adam_m" in f.files:
                 self.native.m = torch.from_numpy(f["adam_m"]).to(self.native.device)
                 self.native.v = torch.from_numpy(f["adam_v"]).to(self.native.device)
-        st = os.path.join(d, "state.json")
-        if os.path.exists(st):
-            with open(st) as f:
-                s = json.load(f)
-            self.g_step = int(s.get("global_step", self.g_step))
-            self.native.step = int(s.get("adam_step", self.native.step))
+            if saved is not None:
+                # no state array: saved before the first update (the next one starts from zeros)
+                self.native.opt_state = torch.from_numpy(f["optimizer_state"]).to(self.native.device) \
+                    if "optimizer_state" in f.files else None
+                self.native.opt = opt
+                opt.iterations = int(saved["iterations"])
+        self.g_step = int(s.get("global_step", self.g_step))
+        self.native.step = int(s.get("adam_step", self.native.step))
 
     def close(self):
         for f in (getattr(self, "csv_file_train", None), getattr(self, "csv_file_val", None)):

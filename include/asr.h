@@ -551,6 +551,38 @@ int asr_adam_update(float* params, const float* grads, float* m, float* v, long 
                     float beta1, float beta2, float eps, long step, float grad_scale,
                     asr_stream_t stream);
 
+/* The tf.keras.optimizers of TF 1.12 (Keras 2.1.6-tf) behind Model.compile /
+ * fit: one launch per update whatever the optimiser, fp32, no host
+ * synchronisation.  Additional exports of ABI 12; asr_adam_update is unchanged.
+ * With g = grads * grad_scale:
+ *   SGD      v = momentum*m - lr*g;  m <- v;
+ *            p <- p + momentum*v - lr*g with ASR_OPT_NESTEROV, else p <- p + v
+ *   Adam     lr_t = lr*sqrt(1 - beta_2^step)/(1 - beta_1^step) (host, double);
+ *            m <- beta_1 m + (1 - beta_1) g;  v <- beta_2 v + (1 - beta_2) g^2;
+ *            with ASR_OPT_AMSGRAD  vhat <- max(vhat, v), p <- p - lr_t m/(sqrt(vhat) + eps),
+ *            else p <- p - lr_t m/(sqrt(v) + eps): the bits of asr_adam_update
+ *   RMSprop  a <- rho a + (1 - rho) g^2;  p <- p - lr g/(sqrt(a) + eps)
+ * Keras' decay is the host's: it passes lr = lr0 / (1 + decay * iterations). */
+enum { ASR_OPT_SGD = 0, ASR_OPT_ADAM = 1, ASR_OPT_RMSPROP = 2 };
+enum { ASR_OPT_NESTEROV = 1 /* SGD */, ASR_OPT_AMSGRAD = 2 /* Adam */ };
+typedef struct asr_optimizer_config {
+  int kind, flags;
+  float lr;         /* the host has already applied Keras' decay */
+  float a, b;       /* SGD: momentum, -;  Adam: beta_1, beta_2;  RMSprop: rho, - */
+  float eps;
+  long step;        /* 1-based update count (Adam's bias correction); >= 1 */
+  float grad_scale; /* g is multiplied by it first (1/world) */
+} asr_optimizer_config;
+/* Host only: the n-float state buffers the optimiser needs (SGD 1: m; Adam 2:
+ * m, v; Adam + AMSGRAD 3: m, v, vhat; RMSprop 1: a), or -1 for an unknown kind
+ * or a flag that does not belong to the kind. */
+int asr_optimizer_slots(int kind, int flags);
+/* state: [slots][n] floats, caller-owned, zero-initialised before the first
+ * update.  ASR_E_ARG before any launch for a null pointer, n < 0, step < 1, an
+ * unknown kind or a flag that does not belong to the kind; n == 0 is ASR_OK. */
+int asr_optimizer_update(const asr_optimizer_config* cfg, float* params, const float* grads,
+                         float* state, long n, asr_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Training-loop metrics, accumulated on the device (no per-step host sync).
  * ---------------------------------------------------------------------- */
