@@ -17,7 +17,12 @@
  *     *_workspace_bytes queries;
  *   - every entry point returns 0 on success and a negative ASR_E* code on
  *     failure; asr_last_error() returns a thread-local message.  Nothing
- *     throws across the ABI.
+ *     throws across the ABI;
+ *   - buffer contract (every section below restates its part; enforced by
+ *     tests/test_gpu_buffers.py): what an output or a workspace holds before a
+ *     call is irrelevant (no call reads a byte of them that it has not written
+ *     itself), relu masks need not be pre-zeroed, and no byte outside the
+ *     documented size of any buffer, input or output, is read or written.
  *
  * Each declaration cites the reference interface it replaces.
  */
@@ -129,7 +134,10 @@ long asr_wpack_elems(int C);
  *                      fixed offset through a deep stack; otherwise round to
  *                      nearest.  Deterministic; restated bit-exactly by
  *                      tests/helpers.py w_bf16_balanced;
- *   dtype == ASR_F32:  w_out (float) gets plain HWIO [3][3][C][C]. */
+ *   dtype == ASR_F32:  w_out (float) gets plain HWIO [3][3][C][C].
+ * Buffers: every element of every layer of w_out is written whatever it held;
+ * with strides above a layer's size the elements between layers are neither
+ * read (theta) nor written (w_out). */
 int asr_theta_to_w(const float* theta, long theta_stride, int L, int C, const int32_t* w_src,
                    float gamma, void* w_out, long w_stride, int dtype, asr_stream_t stream);
 
@@ -156,7 +164,11 @@ int asr_theta_to_w(const float* theta, long theta_stride, int L, int C, const in
  * widths).  asr_conv_backward_workspace_bytes stays <= 64 MB at C >= 128 for
  * every N, H, W (the weight gradient writes at most 48 MB of slabs).
  * Replaces Conv2DAntisymmetric3By3.call (…3By3.py:157-171) and
- * single_layer_identity_block's relu/scale/add (tfkeras_resnets.py:89-92). */
+ * single_layer_identity_block's relu/scale/add (tfkeras_resnets.py:89-92).
+ * Buffers: y and every byte of mask up to asr_mask_bytes (padding bits
+ * included) are overwritten whatever they held, mask need not be pre-zeroed,
+ * and nothing outside x, w, bias, y and mask at their documented sizes is
+ * read or written. */
 int asr_conv_forward(int mode, const void* x, void* y, uint8_t* mask, const void* w,
                      const float* bias, float h, int N, int H, int W, int C, int dtype,
                      asr_stream_t stream);
@@ -171,7 +183,14 @@ long asr_mask_bytes(int N, int H, int W, int C);
  *   (device copy of asr_param_map's theta_dst); db = sum_p dz.
  * dtheta / dbias / dx may be NULL to skip that output; dw_hwio (float
  * [3][3][C][C], may be NULL) receives the unprojected dW.
- * ws: caller workspace of asr_conv_backward_workspace_bytes bytes. */
+ * ws: caller workspace of asr_conv_backward_workspace_bytes bytes.
+ * Buffers: the contents of ws and of the outputs before the call are
+ * irrelevant (the slab reduction reads exactly the rows this call wrote), each
+ * requested output is the same bits whichever others are requested, and
+ * nothing outside the documented sizes (ws: the queried bytes) is read or
+ * written.  The same holds for the stack calls declared next: with strides
+ * larger than a layer, the bytes between consecutive layers are neither read
+ * nor written. */
 /* A stack of L Euler blocks in one call (the deep-stack path, BASELINE
  * config C3: single_layer_identity_block applied L times,
  * tfkeras_resnets.py:579-582).  Layer l reads x_l (x0 for l = 0) and writes
@@ -229,6 +248,9 @@ int asr_conv_backward(int mode, const void* dy, const void* x, const uint8_t* ma
  * W HWIO [k,k,C,C]; maps of k*k*C*C entries.  The antisymmetric kinds keep A^T = -A + 2 gamma I, so
  * asr_conv_backward_k takes the forward W (else W_bwd of
  * asr_param_map_transpose_k with gamma 0), as asr_conv_backward.
+ * Buffers as asr_conv_forward / asr_conv_backward: prior contents of outputs,
+ * mask and ws are irrelevant, mask need not be pre-zeroed, nothing outside the
+ * documented sizes is read or written.
  * ---------------------------------------------------------------------- */
 long asr_theta_count_k(int C, int kernel_size, int kind, int antisymmetric);
 int asr_param_map_k(int C, int kernel_size, int kind, int antisymmetric, int32_t* w_src, int32_t* theta_dst);
@@ -270,6 +292,11 @@ int asr_conv_backward_k(int mode, int kernel_size, const float* dy, const float*
  *     48 MB of slabs and by 256, so the workspace stays <= 64 MB for every
  *     supported shape (49.8 MB at k = 7, C = 64: 59 slabs of 803 KB); 0
  *     outside the supported set.
+ *   Buffers as the fp32 pair: prior contents of outputs, mask, w_pack and ws
+ *     are irrelevant (asr_theta_to_w_k_bf16 writes the pack's zero padding
+ *     itself and, with w_stride above a layer's elements, leaves the bytes
+ *     between layers alone), nothing outside the documented sizes is read or
+ *     written.
  * ---------------------------------------------------------------------- */
 long asr_wpack_elems_k(int C, int kernel_size);
 int asr_theta_to_w_k_bf16(const float* theta, long theta_stride, int L, int C, int kernel_size, const int32_t* w_src,
@@ -290,7 +317,9 @@ int asr_conv_backward_k_bf16(int mode, int kernel_size, const void* dy, const vo
  *   y    = x + h*relu(conv(xmid,W)+b)       mask2 = [conv(xmid,W)+b > 0]
  * Each stage is the fused Euler kernel (the second takes its residual from x).
  * xmid and both masks are kept for the backward; masks may be NULL for
- * inference.
+ * inference.  Buffers: prior contents of xmid, y, the masks (not pre-zeroed),
+ * the backward's outputs and its ws are irrelevant; nothing outside the
+ * documented sizes is read or written (asr_rk2_stack_* likewise).
  * --------------------------------------------------------------------- */
 int asr_rk2_forward(const void* x, void* xmid, void* y, uint8_t* mask1, uint8_t* mask2, const void* w,
                     const float* bias, float h, int N, int H, int W, int C, int dtype,
@@ -340,6 +369,12 @@ int asr_rk2_stack_backward(const void* dyL, const void* xs, const void* xmids, l
  *   fc kernel [C,K], fc bias [K].
  * C and num_classes above 256 return ASR_E_UNSUPPORTED (the head runs one
  * 256-thread workgroup per image), as asr_stages_check does.
+ * Buffers: a workspace holds nothing a step depends on but what
+ * asr_net_prepare uploaded and what the step itself wrote before reading it
+ * (the masks and slab rows carved from it are never assumed zero), so a step
+ * gives the same bits on a fresh, a recycled or a just-used workspace; grads,
+ * loss and probs are overwritten; nothing outside asr_net_workspace_bytes and
+ * the documented sizes is read or written.
  * --------------------------------------------------------------------- */
 typedef struct asr_net_config {
   int N, H, W, Cin, C, L, num_classes;
@@ -492,6 +527,9 @@ int asr_debug_stack_backward(int grid);
  *     y = relu(conv_3x3(x, K2, stride) + b2) + conv_1x1(x, K1, stride) + b1
  * (the 3x3 'same' with TF's asymmetric stride padding, the 1x1 'valid'), then
  * GAP + Dense softmax.  fp32 (the reference's precision); no BN / pooling.
+ * Buffers as the single-block network: prior contents of outputs, masks and
+ * workspaces (the transition's and asr_stages_workspace_bytes) are irrelevant,
+ * and nothing outside the documented sizes is read or written.
  * ---------------------------------------------------------------------- */
 
 /* The transition alone.  x [N,H,W,Ci] -> y [N,Ho,Wo,Co], Ho = ceil(H/stride);
@@ -562,7 +600,10 @@ int asr_adam_update(float* params, const float* grads, float* m, float* v, long 
  *            with ASR_OPT_AMSGRAD  vhat <- max(vhat, v), p <- p - lr_t m/(sqrt(vhat) + eps),
  *            else p <- p - lr_t m/(sqrt(v) + eps): the bits of asr_adam_update
  *   RMSprop  a <- rho a + (1 - rho) g^2;  p <- p - lr g/(sqrt(a) + eps)
- * Keras' decay is the host's: it passes lr = lr0 / (1 + decay * iterations). */
+ * Keras' decay is the host's: it passes lr = lr0 / (1 + decay * iterations).
+ * Buffers: params and state are read-modify-write over exactly n and slots * n
+ * floats, grads is read over n; nothing outside them is read or written
+ * (asr_adam_update likewise). */
 enum { ASR_OPT_SGD = 0, ASR_OPT_ADAM = 1, ASR_OPT_RMSPROP = 2 };
 enum { ASR_OPT_NESTEROV = 1 /* SGD */, ASR_OPT_AMSGRAD = 2 /* Adam */ };
 typedef struct asr_optimizer_config {
@@ -686,7 +727,10 @@ typedef struct asr_aug_plan {
  * The device table is NOT validated on the host (no synchronisation): items
  * must hold 0 <= src < n_src and windows inside the source.  The kernel clamps
  * src, the window size and its origin into the array, so a bad table gives
- * wrong pixels, never an access outside src. */
+ * wrong pixels, never an access outside src.
+ * Buffers: every byte of dst (the zero border of a padded resize included) is
+ * written whatever it held; nothing outside src, items and dst is read or
+ * written. */
 int asr_augment_batch(const void* src, long n_src, const asr_aug_plan* plan, const asr_aug_item* items, int N,
                       void* dst, asr_stream_t stream);
 

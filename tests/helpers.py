@@ -1,5 +1,44 @@
-"""Shared test utilities: bf16 rounding in numpy, mask decoding, tolerances."""
+"""Shared test utilities: bf16 rounding in numpy, mask decoding, tolerances, guarded buffers."""
 import numpy as np
+
+GUARD = 256  # bytes on either side of a carved buffer (keeps the allocation's 256-byte alignment for the view)
+
+
+def carve(shape, dtype, dev, fill=0xA5, guard_fill=0xA5):
+    """A contiguous tensor of `shape` and `dtype` of exactly its documented byte size, GUARD bytes into
+    a larger uint8 buffer: (buffer, view).  The interior bytes are `fill`, the GUARD bytes on either
+    side `guard_fill` (0xFF: NaN as fp32 and as bf16, all-ones mask bits, -1 as int32)."""
+    import torch
+    shape = (int(shape),) if np.isscalar(shape) else tuple(int(s) for s in shape)
+    n = int(np.prod(shape, dtype=np.int64)) * torch.empty(0, dtype=dtype).element_size()
+    buf = torch.empty(GUARD + n + GUARD, dtype=torch.uint8, device=dev)
+    buf[:GUARD] = guard_fill
+    buf[GUARD:GUARD + n] = fill
+    buf[GUARD + n:] = guard_fill
+    return buf, buf[GUARD:GUARD + n].view(dtype).view(shape)
+
+
+def carve_like(t, guard_fill=0xFF):
+    """An input buffer: the contents of the tensor `t` (moved to its device's carved buffer bit for
+    bit), exactly its byte size, between two guards of `guard_fill`: (buffer, view)."""
+    t = t.contiguous()
+    buf, view = carve(tuple(t.shape), t.dtype, t.device, 0, guard_fill)
+    view.copy_(t)
+    return buf, view
+
+
+def guards_intact(buf, nbytes, what, guard_fill=0xA5):
+    """Assert that the GUARD bytes before and after the `nbytes` interior of a carved buffer still hold
+    `guard_fill`.  Only the two guard slices are copied to the host (workspaces reach tens of MB)."""
+    assert buf.numel() == GUARD + nbytes + GUARD, f"{what}: not a carved buffer of {nbytes} bytes"
+    before = buf[:GUARD].cpu().numpy()
+    after = buf[GUARD + nbytes:].cpu().numpy()
+    bad = np.flatnonzero(before != guard_fill)
+    assert bad.size == 0, (f"{what}: bytes before the buffer overwritten ({bad.size} of {GUARD}, nearest "
+                           f"{GUARD - int(bad[-1])} bytes before its start)")
+    bad = np.flatnonzero(after != guard_fill)
+    assert bad.size == 0, (f"{what}: bytes after the buffer overwritten ({bad.size} of {GUARD}, first "
+                           f"{int(bad[0])} bytes past its end)")
 
 
 def bf16_round(x):

@@ -31,7 +31,7 @@ fused results equal the per-block kernels' bit for bit (y, masks, dx0, dparams).
 import numpy as np
 import pytest
 
-from helpers import assert_close, decode_mask, rel_l2, w_bf16_balanced
+from helpers import GUARD, assert_close, carve, decode_mask, guards_intact, rel_l2, w_bf16_balanced
 from oracle import asr_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -227,20 +227,13 @@ def test_stage_backward_layers_vs_oracle(rt, dtype, HW, C, N, L, gamma):
     assert torch.equal(dx0, dy) and same_dp, (r2, mx, ul, same_dp)
 
 
-GUARD = 256  # bytes on either side of a carved buffer
-
-
 def _carve(shape, dtype, dev):
     """A tensor of `shape` in the middle of a larger buffer filled with 0xA5 bytes: (buffer, view)."""
-    n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
-    buf = torch.full((GUARD + n + GUARD,), 0xA5, dtype=torch.uint8, device=dev)
-    return buf, buf[GUARD:GUARD + n].view(dtype).view(shape)
+    return carve(shape, dtype, dev, 0xA5, 0xA5)
 
 
 def _guards_intact(buf, what):
-    g = buf.cpu().numpy()
-    assert (g[:GUARD] == 0xA5).all(), f"{what}: bytes before the buffer overwritten"
-    assert (g[-GUARD:] == 0xA5).all(), f"{what}: bytes after the buffer overwritten"
+    guards_intact(buf, buf.numel() - 2 * GUARD, what, 0xA5)
 
 
 @pytest.mark.parametrize("dtype,HW,C", [("bf16", 8, 32), ("f32", 16, 32)])
