@@ -9,7 +9,7 @@
 
 namespace asr {
 
-// conv modes of the fp32 kernels (asr_conv_f32.hip; conv_f32's fmode, asr_api.hip's dispatch)
+// conv modes of the 3x3 block kernels (asr_conv_f32.hip: conv_f32's fmode, asr_api.hip's dispatch; asr_conv_bf16.hip)
 enum { F_EULER = 0, F_CONV = 1, F_RELU = 2, B_EULER = 3, B_CONV = 4 };
 
 // Most weight-gradient slabs one launch writes: the grid bound of the block and
@@ -123,6 +123,14 @@ bool conv32_fused_bwd_supported(int W, int C);
 int conv32_bwd_fused(const float* dy, const uint8_t* mask, float h, const float* x, const float* w, float two_gamma,
                      const float* extra, bool skip_dy, int N, int H, int W, int C, float* dx, bool need_w,
                      float* slabs, int* nslabs, hipStream_t s);
+// wgrad_layers' fp32 half (k_wgrad32, blockIdx.y = layer; dz = h dy [relu bit] formed in the kernel)
+int wgrad32_layers(const float* x0, long x_stride, const float* dys, long d_stride, const uint8_t* masks,
+                   long mask_stride, float h, int N, int H, int W, int C, int L, float* slabs, long slab_stride,
+                   int* nslabs, hipStream_t s);
+// bf16 <-> fp32, elementwise (n a multiple of 8)
+int convert_bf16_f32(const void* src, void* dst, long n, int to_f32, hipStream_t s);
+
+// ---- asr_conv_bf16.hip -----------------------------------------------------
 // bf16 Euler blocks and bare convs at any width the 16-pixel MFMA tile takes (W = 8 or W % 16 == 0): the
 // multi-stage nets' path, and every single-stage shape off W = 32
 bool convb_supported(int W, int C);
@@ -133,8 +141,13 @@ int convb_forward(const void* x, void* y, uint8_t* mask, const void* w, const fl
 int convb_backward(const void* dy, const uint8_t* mask, const void* x, const void* w, float h, float two_gamma, int N,
                    int H, int W, int C, void* dx, bool need_w, float* slabs, int* nslabs, hipStream_t s,
                    bool conv_only = false);
-// bf16 <-> fp32, the image-resident stages (all L blocks of a 16 x 16 x 32 or 8 x 8 x 64 stage in one launch)
-int convert_bf16_f32(const void* src, void* dst, long n, int to_f32, hipStream_t s);
+// wgrad_layers' bf16 half (k_wgradb over bands, blockIdx.y = layer), C in {16, 32, 64}, W in {32, 16, 8}
+int wgradb_layers(const bf16* x0, long x_stride, const bf16* dys, long d_stride, const uint8_t* masks, long mask_stride,
+                  float h, int N, int H, int W, int C, int L, float* slabs, long slab_stride, int* nslabs,
+                  hipStream_t s);
+
+// ---- asr_stage_img.hip -----------------------------------------------------
+// the image-resident stages (all L blocks of a 16 x 16 x 32 or 8 x 8 x 64 stage in one launch);
 // dtype (ASR_BF16 / ASR_F32) picks the kernels; activations, W and dys are of that type
 bool stage_img_supported(int H, int W, int C, int dtype);
 int stage_img_forward(int dtype, const void* x0, void* ys, long y_stride, uint8_t* masks, long mask_stride,

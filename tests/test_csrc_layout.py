@@ -6,9 +6,11 @@
     under: no .hip file re-declares it (a copy's default arguments could drift
     without any error);
   * the shared constants (the fp32 conv modes, the slab caps) are defined in
-    asr_internal.h only.
+    asr_internal.h only;
+  * _build.SOURCES, the one list of HIP sources, is the set of csrc/*.hip.
 """
 import glob
+import importlib.util
 import os
 import re
 import shutil
@@ -84,6 +86,16 @@ def test_shared_functions_declared_once_defined_where_grouped():
             if depth == 0:
                 break
         assert t[i:].lstrip().startswith("{"), f"{name} in {want} is a declaration, not the definition"
+
+
+def test_build_sources_are_the_hip_files_of_csrc():
+    """_build.SOURCES is the one list of HIP sources (the build, tests/test_isa.py and tools/build_variants.sh
+    read it): every *.hip of csrc/ once, and nothing else."""
+    spec = importlib.util.spec_from_file_location("_asr_build", os.path.join(os.path.dirname(CSRC), "_build.py"))
+    build = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(build)
+    assert len(set(build.SOURCES)) == len(build.SOURCES)
+    assert set(build.SOURCES) == set(HIP)
 
 
 def test_shared_constants_defined_in_the_header_only():

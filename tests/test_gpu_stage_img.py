@@ -1,8 +1,8 @@
 """GPU parity of the image-resident stage kernels, layer by layer, through the
 block-stack ABI (asr_block_stack_forward / _backward): k_stagef / k_stageb
 (bf16 at 16x16x32, 8x8x64, 8x8x32), k_stagef32 / k_stageb32 (fp32 at 16x16x32,
-8x8x64) and the all-layers weight gradients of wgrad_layers (k_wgradb / k_wgrad32)
-(asr_conv_f32.hip).  The stages executor runs the same kernels
+8x8x64) and the all-layers weight gradients of wgrad_layers (asr_stage_img.hip;
+k_wgradb of asr_conv_bf16.hip / k_wgrad32 of asr_conv_f32.hip).  The stages executor runs the same kernels
 (test_gpu_stages.py checks them only through whole networks).
 
 Every layer is compared with the fp64 oracle's Euler step

@@ -28,6 +28,7 @@ LDS reads and LDS-DMA, which the compiler cannot see:
     bytes (the numbers of the measured production build, with the reason);
     any growth fails here and needs a new audit and a GPU parity run.
 """
+import importlib.util
 import os
 import re
 import shutil
@@ -47,8 +48,17 @@ import asm_vmem_audit  # noqa: E402
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-w"]
-KERNEL_SOURCES = ["asr_block_mfma.hip", "asr_deep16.hip", "asr_stem_head.hip", "asr_conv_f32.hip", "asr_theta.hip", "asr_stages.hip",
-                  "asr_api.hip"]
+
+
+def _build_sources():
+    """_build.SOURCES, the one list of HIP sources (loaded by path: importing the package would build the library)"""
+    spec = importlib.util.spec_from_file_location("_asr_build", os.path.join(os.path.dirname(CSRC), "_build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return list(mod.SOURCES)
+
+
+KERNEL_SOURCES = _build_sources()  # every product source
 
 # (kernel-name regex) -> (max VGPR spills, max scratch bytes, why)
 SPILL_ALLOW = {
@@ -81,7 +91,7 @@ def _compile(src, out):
 def asm_files(tmp_path_factory):
     d = tmp_path_factory.mktemp("isa")
     jobs = [(os.path.join(CSRC, s), str(d / (s + ".s"))) for s in KERNEL_SOURCES]
-    with ThreadPoolExecutor(len(jobs)) as pool:
+    with ThreadPoolExecutor(min(len(jobs), os.cpu_count() or 1)) as pool:
         return list(pool.map(lambda a: _compile(*a), jobs))
 
 

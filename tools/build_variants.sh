@@ -1,14 +1,16 @@
 #!/bin/bash
-# development: libasr variants for A/B timing.  usage: tools/build_variants.sh NAME "-DFLAG=.." [NAME "-D.."]...
-# NAME=head builds the committed sources (git HEAD) instead of the working tree.
+# development: libasr variants for A/B timing and the trace builds (tools/blktrace.py, stacktrace.py, tracebench.py,
+# stampbench.py).  usage: tools/build_variants.sh NAME "-DFLAG=.." [NAME "-D.."]...
+# NAME=head builds the committed sources (git HEAD) instead of the working tree.  The sources are _build.SOURCES.
 cd "$(dirname "$0")/.."
-S=differential_equations_resnet_amd/csrc
+P=differential_equations_resnet_amd
+S=$P/csrc
 while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
-  src=$S
-  if [ $name = head ]; then rm -rf /tmp/asr_head && mkdir -p /tmp/asr_head && git archive HEAD $S include | tar -x -C /tmp/asr_head && src=/tmp/asr_head/$S; fi
-  /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared $flags -o build_abl_$name.so \
-    $src/asr_theta.hip $src/asr_block_mfma.hip $src/asr_conv_f32.hip $src/asr_stem_head.hip $src/asr_api.hip $src/asr_dist.hip $src/asr_deep16.hip $src/asr_stages.hip &
+  root=.
+  if [ $name = head ]; then root=$(mktemp -d) && git archive HEAD $P/_build.py $S include | tar -x -C $root; fi
+  srcs=$(cd $root/$P && python -c "import _build; print(' '.join('$root/$S/' + s for s in _build.SOURCES))")
+  /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared $flags -o build_abl_$name.so $srcs &
 done
 wait
 ls -la build_abl_*.so

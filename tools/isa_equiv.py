@@ -2,15 +2,20 @@
 instruction streams and the same kernel metadata?  (A refactor claimed neutral
 must: round 4's switch cleanup 6c75dab compiles every stack kernel
 bit-identically to f540cc2, the measured tree before it.)  Labels are
-renumbered, comments and directives dropped.  Prints one same/DIFF line per
-kernel (a kernel of one side only is a DIFF) and a summary; exit status 1 on
-any difference.  --alias REGEX=REPLACEMENT (repeatable) rewrites the kernel
-symbols of both sides with re.sub before they are matched: a renamed or
-re-parameterised kernel against its predecessor.  A kernel whose instructions
-differ comes with the number of differing lines.
-usage: python tools/isa_equiv.py [--alias REGEX=REPLACEMENT ...] REV_A REV_B [source.hip ...]
-       (default: every product source)"""
+renumbered, comments and directives dropped.  Each side's sources are its own
+csrc/*.hip and kernels are matched by symbol across the whole tree, so a kernel
+moved to another file is `same`; a symbol that two sources of one side define
+(a kernel template instantiated in two translation units) is a DIFF.  Prints
+one same/DIFF line per kernel with its file on each side (a kernel of one side
+only is a DIFF) and a summary; exit status 1 on any difference.
+--alias REGEX=REPLACEMENT (repeatable) rewrites the kernel symbols of both
+sides with re.sub before they are matched: a renamed or re-parameterised kernel
+against its predecessor.  A kernel whose instructions differ comes with the
+number of differing lines.
+usage: python tools/isa_equiv.py [--alias REGEX=REPLACEMENT ...] REV_A REV_B
+       (a revision, or a directory holding a tree: `.` is the working tree)"""
 import difflib
+import glob
 import os
 import re
 import subprocess
@@ -20,8 +25,6 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "differential_equations_resnet_amd/csrc"
-SOURCES = ["asr_theta.hip", "asr_block_mfma.hip", "asr_conv_f32.hip", "asr_conv_kxk.hip", "asr_stem_head.hip",
-           "asr_api.hip", "asr_dist.hip", "asr_deep16.hip", "asr_stages.hip"]
 META = ["vgpr_count", "sgpr_count", "vgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size"]
 
 
@@ -62,6 +65,9 @@ def compile_tree(tree, src, out):
 
 
 def export(rev, d):
+    """the tree of a git revision, or `rev` itself where it is a directory (a working tree)"""
+    if os.path.isdir(rev):
+        return rev
     dst = os.path.join(d, rev)
     os.makedirs(dst, exist_ok=True)
     tar = subprocess.run(["git", "-C", ROOT, "archive", rev, CSRC, "include"], check=True, capture_output=True).stdout
@@ -87,31 +93,51 @@ def differing_lines(a, b):
                if op != "equal")
 
 
-def compare(tree_a, tree_b, srcs, d, aliases=()):
+def sources(tree):
+    """the tree's own HIP sources"""
+    return sorted(os.path.basename(p) for p in glob.glob(os.path.join(tree, CSRC, "*.hip")))
+
+
+def side(tree, tag, d, aliases):
+    """({kernel symbol: (source, instructions, metadata or None)}, {symbol defined twice: its sources}, number of
+    sources) of every HIP source of `tree`"""
+    srcs = sources(tree)
+    with ThreadPoolExecutor(min(len(srcs), os.cpu_count() or 1, 16)) as pool:
+        res = list(pool.map(lambda s: compile_tree(tree, s, os.path.join(d, f"{tag}_{s}.s")), srcs))
+    table, twice = {}, {}
+    for src, (ks, ms) in zip(srcs, res):
+        ms = renamed(ms, aliases)
+        for k, body in renamed(ks, aliases).items():
+            if k in table:
+                twice.setdefault(k, [table[k][0]]).append(src)
+            table[k] = (src, body, ms.get(k))
+    return table, twice, len(srcs)
+
+
+def compare(tree_a, tree_b, d, aliases=()):
     """Print one line per kernel and the summary; the number of differing kernels."""
-    jobs = [(t, s, os.path.join(d, f"{i}_{s}.s")) for s in srcs for i, t in enumerate((tree_a, tree_b))]
-    with ThreadPoolExecutor(min(len(jobs), os.cpu_count() or 1, 16)) as pool:
-        res = [tuple(renamed(t, aliases) for t in r) for r in pool.map(lambda j: compile_tree(*j), jobs)]
+    (ta, dup_a, na), (tb, dup_b, nb) = side(tree_a, "a", d, aliases), side(tree_b, "b", d, aliases)
     total = diffs = 0
-    for n, src in enumerate(srcs):
-        (ka, ma), (kb, mb) = res[2 * n], res[2 * n + 1]
-        for k in sorted(set(ka) | set(kb)):
-            if k not in ka or k not in kb:
-                tag = "DIFF (only in %s)" % ("A" if k in ka else "B")
-            elif ka[k] != kb[k]:
-                tag = "DIFF (instructions: %d lines of %d -> %d differ)" % (differing_lines(ka[k], kb[k]), len(ka[k]),
-                                                                          len(kb[k]))
-            elif k not in ma or k not in mb:
-                tag = "DIFF (no metadata entry in %s)" % " and ".join(s for s, m in (("A", ma), ("B", mb)) if k not in m)
-            elif ma[k] != mb[k]:
-                tag = "DIFF (metadata: " + ", ".join(f"{m} {ma[k][m]} -> {mb[k][m]}" for m in META
-                                                     if ma[k][m] != mb[k][m]) + ")"
-            else:
-                tag = "same"
-            total += 1
-            diffs += tag != "same"
-            print(f"{tag} {src} {k[:90]}")
-    print(f"isa_equiv: {total} kernels in {len(srcs)} sources, {total - diffs} same, {diffs} DIFF")
+    for k in sorted(set(ta) | set(tb)):
+        (fa, ka, ma), (fb, kb, mb) = ta.get(k, ("-", None, None)), tb.get(k, ("-", None, None))
+        if k in dup_a or k in dup_b:
+            tag = "DIFF (defined in " + "; ".join(f"{' and '.join(dup[k])} of {s}" for s, dup in (("A", dup_a), ("B", dup_b))
+                                                  if k in dup) + ")"
+        elif ka is None or kb is None:
+            tag = "DIFF (only in %s)" % ("A" if kb is None else "B")
+        elif ka != kb:
+            tag = "DIFF (instructions: %d lines of %d -> %d differ)" % (differing_lines(ka, kb), len(ka), len(kb))
+        elif ma is None or mb is None:
+            tag = "DIFF (no metadata entry in %s)" % " and ".join(s for s, m in (("A", ma), ("B", mb)) if m is None)
+        elif ma != mb:
+            tag = "DIFF (metadata: " + ", ".join(f"{m} {ma[m]} -> {mb[m]}" for m in META if ma[m] != mb[m]) + ")"
+        else:
+            tag = "same"
+        total += 1
+        diffs += tag != "same"
+        print(f"{tag} {fa if fa == fb else fa + ' -> ' + fb} {k[:90]}")
+    print(f"isa_equiv: {total} kernels ({len(ta)} in {na} sources -> {len(tb)} in {nb} sources), {total - diffs} same, "
+          f"{diffs} DIFF")
     return diffs
 
 
@@ -123,4 +149,4 @@ if __name__ == "__main__":
         del args[i:i + 2]
     a, b = args[0], args[1]
     with tempfile.TemporaryDirectory() as d:
-        sys.exit(1 if compare(export(a, d), export(b, d), args[2:] or SOURCES, d, aliases) else 0)
+        sys.exit(1 if compare(export(a, d), export(b, d), d, aliases) else 0)
