@@ -392,7 +392,7 @@ int block_stack_bwd_mfma(void* dbuf0, void* dbuf1, const void* xs, long x_stride
   // co-residency needed: e.g. several processes sharing one device)
   const int lfold = fold && (fchunks + grid - 1) / grid <= 512 ? 2 : L;
   if (lfold_out) *lfold_out = lfold;
-  ASR_TRY(hip_check(hipMemsetAsync(done, 0, (size_t)stack_done_words(L) * 4, s), "hipMemsetAsync"));
+  ASR_TRY(zero_words(done, stack_done_words(L), s));
   unsigned* skipf = done + L + 4;
   const size_t lds = stack_bwd_lds();
 #define ASR_STACK_BWD(RK, PR)                                                                                   \

@@ -502,8 +502,7 @@ static int launch_conv_f32(const void* xin, void* out, uint8_t* mask, const floa
   const long blocks = (tasks + 3) / 4;
   if (blocks > 0x7fffffffL) return fail(ASR_E_ARG, "conv f32: problem too large");
   if (MODE == F_EULER && mask) {
-    const long bytes = ((long)N * H * W * Co + 31) / 32 * 4;
-    ASR_TRY(hip_check(hipMemsetAsync(mask, 0, bytes, s), "hipMemsetAsync(mask)"));
+    ASR_TRY(zero_words(mask, ((long)N * H * W * Co + 31) / 32, s));  // (the kernel ORs its bits in)
   }
   hipLaunchKernelGGL((k_conv_f32<Tout, MODE>), dim3((unsigned)blocks), dim3(256), 0, s, (const float*)xin,
                      (Tout*)out, (uint32_t*)mask, w, bias, h, two_gamma, dy, extra, N, H, W, Ci, Co, K);

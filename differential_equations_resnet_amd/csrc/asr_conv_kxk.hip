@@ -280,20 +280,25 @@ int launch_convk(const bf16* xin, bf16* out, uint8_t* mask, const bf16* w, const
   using G = KxkBand<C, W, K>;
   constexpr size_t lds = G::lds(MODE);
   static_assert(lds <= 160 * 1024, "bf16 k x k band: LDS per workgroup");
-  if (lds > 64 * 1024)  // above the default dynamic-LDS limit
-    ASR_TRY(hip_check(hipFuncSetAttribute((const void*)k_convk<C, W, K, MODE>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                      "hipFuncSetAttribute"));
   const long items = (long)N * ((H + G::BR - 1) / G::BR);
-  // persistent workgroups per CU: what registers and LDS keep resident (1 if the runtime cannot say)
-  static int resident = 0;
-  if (resident == 0) {
+  // once per instantiation and device (a device beyond the table: every call): the dynamic-LDS limit, raised
+  // where the band needs more than the default, and the persistent workgroups per CU: what registers and
+  // LDS keep resident (1 if the runtime cannot say)
+  static int resident[64];
+  int dev = 0, uncached = 0;
+  ASR_TRY(hip_check(hipGetDevice(&dev), "hipGetDevice"));
+  int* res = dev >= 0 && dev < 64 ? &resident[dev] : &uncached;
+  if (*res == 0) {
+    if (lds > 64 * 1024)  // above the default dynamic-LDS limit
+      ASR_TRY(hip_check(hipFuncSetAttribute((const void*)k_convk<C, W, K, MODE>,
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                        "hipFuncSetAttribute"));
     int nblk = 0;
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_convk<C, W, K, MODE>, 256, lds);
-    resident = (e == hipSuccess && nblk > 0) ? nblk : 1;
+    *res = (e == hipSuccess && nblk > 0) ? nblk : 1;
     if (e != hipSuccess) (void)hipGetLastError();
   }
-  const int per_cu = std::min(4, resident);
+  const int per_cu = std::min(4, *res);
   const long grid = std::max<long>(1, std::min<long>(items, (long)per_cu * launch_cus()));
   hipLaunchKernelGGL((k_convk<C, W, K, MODE>), dim3((unsigned)grid), dim3(256), lds, s, xin, out, mask, w, bias, h,
                      two_gamma, N, H, dmask);

@@ -29,6 +29,10 @@ constexpr int kMaxStemSlabs = kMaxBlockSlabs;
 int cu_count();
 // the same for sizing a grid or a workspace: where the query fails, an MI355X's 256
 inline int launch_cus() { const int cus = cu_count(); return cus > 0 ? cus : 256; }
+// p[0 .. words) = 0 (32-bit words, p 4-byte aligned) by a kernel on s.  Not hipMemsetAsync: recorded into a HIP
+// graph, its memset node was seen to run out of order with the work enqueued before the replay
+// (tests/test_gpu_streams.py: relu masks keeping bits of their previous contents), a kernel node is not.
+int zero_words(void* p, long words, hipStream_t s);
 // A network / stage workspace must live on the current device: its layout (the
 // weight-gradient slab rows, hence every offset after them) follows the CU
 // count of the device current when it was sized, and the kernels size their

@@ -70,6 +70,18 @@ int cu_count() {
   return cus;
 }
 
+__global__ void k_zero_words(uint32_t* __restrict__ p, long words) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < words; i += (long)gridDim.x * blockDim.x) p[i] = 0u;
+}
+
+int zero_words(void* p, long words, hipStream_t s) {
+  if (words <= 0) return ASR_OK;
+  const unsigned grid = (unsigned)std::min<long>((words + 255) / 256, 1024);
+  hipLaunchKernelGGL(k_zero_words, dim3(grid), dim3(256), 0, s, (uint32_t*)p, words);
+  ASR_LAUNCH_CHECK("k_zero_words");
+  return ASR_OK;
+}
+
 // ---------------------------------------------------------------------------
 // host: element maps
 // ---------------------------------------------------------------------------

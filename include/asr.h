@@ -12,9 +12,16 @@
  *   - plain pointers and sizes only; every pointer is a device pointer unless
  *     the comment says "host";
  *   - activations NHWC, kernels HWIO [3][3][C_in][C_out] (reference layout);
- *   - every call is a stateless launch on the caller's stream; nothing here
- *     allocates device memory: workspaces are caller-owned, sized by the
- *     *_workspace_bytes queries;
+ *   - stream contract (enforced by tests/test_gpu_streams.py on the GPU and by
+ *     tests/test_streams_cpu.py over the sources): every call is a stateless
+ *     launch on the caller's stream: every kernel launch and asynchronous copy
+ *     of a call is issued on the stream it was passed and nowhere else.  No
+ *     call synchronises or allocates (workspaces are caller-owned, sized by
+ *     the *_workspace_bytes queries), apart from the entry points marked
+ *     "blocking; not capturable" (asr_net_prepare, asr_stages_prepare,
+ *     asr_net_check_status, asr_net_kernel_times, asr_stack_status, and the
+ *     asr_debug_* readers).  Every other call may therefore run on any stream
+ *     beside other work and be recorded into a HIP graph and replayed;
  *   - every entry point returns 0 on success and a negative ASR_E* code on
  *     failure; asr_last_error() returns a thread-local message.  Nothing
  *     throws across the ABI;
@@ -473,7 +480,8 @@ typedef struct asr_net_config {
 
 long asr_net_param_count(const asr_net_config* cfg);
 size_t asr_net_workspace_bytes(const asr_net_config* cfg);
-/* One-time setup of a workspace (uploads the parameter maps; blocking). */
+/* One-time setup of a workspace (uploads the parameter maps with synchronous
+ * copies: blocking; not capturable). */
 int asr_net_prepare(const asr_net_config* cfg, void* ws, size_t ws_bytes);
 /* probs: [N, K] float (softmax outputs, the Model's output). */
 int asr_net_forward(const asr_net_config* cfg, const float* params, const void* images,
@@ -484,7 +492,7 @@ int asr_net_forward(const asr_net_config* cfg, const float* params, const void* 
 int asr_net_forward_backward(const asr_net_config* cfg, const float* params, const void* images,
                              const float* targets, float* grads, float* loss, float* probs,
                              void* ws, size_t ws_bytes, asr_stream_t stream);
-/* Host, blocking (synchronises the stream): ASR_OK, or ASR_E_HIP with the
+/* Host, blocking; not capturable (synchronises the stream): ASR_OK, or ASR_E_HIP with the
  * runtime's error when work on the stream failed (the stream's status only:
  * a pending error of another HIP call on this thread is neither reported nor
  * cleared).  (Since ABI 6 a missed
@@ -492,7 +500,8 @@ int asr_net_forward_backward(const asr_net_config* cfg, const float* params, con
  * speed, see asr_stack_status.) */
 int asr_net_check_status(const asr_net_config* cfg, const void* ws, size_t ws_bytes, asr_stream_t stream);
 
-/* Host, blocking: device times in microseconds of the last asr_net_forward /
+/* Host, blocking; not capturable (waits for the events of that call): device
+ * times in microseconds of the last asr_net_forward /
  * asr_net_forward_backward called with ASR_VARIANT_TIMED: us[0] the L blocks'
  * forward (the single stack launch where one runs), us[1] the L blocks'
  * backward kernels (the single stack launch k_bwd3_stack / k_bwd16_fused
@@ -500,7 +509,8 @@ int asr_net_check_status(const asr_net_config* cfg, const void* ws, size_t ws_by
  * the projection onto theta; -1 for a part that call did not run. */
 int asr_net_kernel_times(float* us);
 
-/* Host, blocking (a device-to-host copy on the current device): the number of
+/* Host, blocking; not capturable (allocates, and copies device to host on the
+ * current device): the number of
  * degraded in-launch slab hand-offs of the C=64 stacked backward (k_bwd3_stack)
  * since the last reset, >= 0 (or a negative error code).  A workgroup whose
  * bounded wait (~1-2 ms) for the other workgroups' weight-gradient slabs of a
@@ -575,6 +585,8 @@ typedef struct asr_stages_config {
 int asr_stages_check(const asr_stages_config* cfg);
 long asr_stages_param_count(const asr_stages_config* cfg);
 size_t asr_stages_workspace_bytes(const asr_stages_config* cfg);
+/* One-time setup of a workspace (uploads every stage's parameter maps with
+ * synchronous copies: blocking; not capturable). */
 int asr_stages_prepare(const asr_stages_config* cfg, void* ws, size_t ws_bytes);
 int asr_stages_forward(const asr_stages_config* cfg, const float* params, const void* images, float* probs,
                        void* ws, size_t ws_bytes, asr_stream_t stream);

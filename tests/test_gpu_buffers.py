@@ -92,6 +92,10 @@ class Bufs:
         self.all.append((buf, _nbytes(v), what, self.fill))
         return v
 
+    def call(self, name, *args):
+        """The launch of a case builder (tests/test_gpu_streams.py records it instead, to issue it later)."""
+        _call(name, *args)
+
     def check(self):
         torch.cuda.synchronize()
         for buf, n, what, g in self.all:
@@ -132,6 +136,15 @@ def _dev(a, bf=False):
     return t.to(torch.bfloat16).contiguous() if bf else t
 
 
+def _rng(seed, salt=None):
+    """The case's generator; with a salt, an independent one (a seed sequence no integer seed equals)."""
+    return np.random.default_rng(seed if salt is None else [seed, salt])
+
+
+def _rand_bytes(rng, *shape, below=256):
+    return _dev(rng.integers(0, below, shape, dtype=np.uint8))
+
+
 def _theta3(C, rng, L=1):
     """test_gpu_kernels._theta / test_gpu_deep16._stack_inputs: the reference's 3by3 initialisation."""
     return np.concatenate([O.flatten(O.init_theta_3by3(C, rng, np.float64)) for _ in range(L)]).astype(np.float32)
@@ -170,14 +183,17 @@ _CONV_DATA = {}
 
 
 class ConvCase:
-    """Operands of one conv case on the GPU (never modified) and the wrapper's results."""
+    """Operands of one conv case on the GPU (never modified) and the wrapper's results.
 
-    def __init__(self, rt, name, dtype, k, shape):
+    With a `salt` (tests/test_gpu_streams.py): another, independent draw of the same operands and
+    nothing computed from them; the backward's mask is then random bits."""
+
+    def __init__(self, rt, name, dtype, k, shape, salt=None):
         N, H, W, C = shape
         self.k, self.shape, self.bf = k, shape, dtype == "bf16"
         self.dt = rt.ASR_BF16 if self.bf else rt.ASR_F32
         self.tdt = rt.torch_dtype(self.dt)
-        rng = np.random.default_rng(sum(map(ord, name)))
+        rng = _rng(sum(map(ord, name)), salt)
         if k == 3:
             self.pm = rt.param_map(C)
             th = _theta3(C, rng)
@@ -190,6 +206,9 @@ class ConvCase:
         self.bias = _dev((rng.standard_normal(C) * 0.1).astype(np.float32))
         self.mb = rt.mask_bytes(N, H, W, C)
         self.theta_dst = self.pm.device(self.x.device)[1]
+        if salt is not None:
+            self.mask = _rand_bytes(rng, self.mb)
+            return
         # the wrapper's results: forward (zeroed mask), then the backward on that mask
         self.want_fwd, self.want_bwd = {}, {}
         for mode in (rt.ASR_MODE_EULER, rt.ASR_MODE_CONV):
@@ -220,10 +239,10 @@ class ConvCase:
         y = B.out(self.shape, self.tdt, "y")
         mask = B.out((self.mb,), torch.uint8, "mask") if euler else None
         if self.k == 3:
-            _call("asr_conv_forward", mode, _p(x), _p(y), _p(mask), _p(w), _p(b), H_STEP, N, H, W, C, self.dt, _stream())
+            B.call("asr_conv_forward", mode, _p(x), _p(y), _p(mask), _p(w), _p(b), H_STEP, N, H, W, C, self.dt, _stream())
         else:
-            _call("asr_conv_forward_k_bf16" if self.bf else "asr_conv_forward_k", mode, self.k, _p(x), _p(y), _p(mask),
-                  _p(w), _p(b), H_STEP, N, H, W, C, _stream())
+            B.call("asr_conv_forward_k_bf16" if self.bf else "asr_conv_forward_k", mode, self.k, _p(x), _p(y), _p(mask),
+                   _p(w), _p(b), H_STEP, N, H, W, C, _stream())
         return {"y": y, "mask": mask}
 
     def backward(self, B, mode, euler, outs=("dx", "dtheta", "dbias", "dw")):
@@ -239,19 +258,19 @@ class ConvCase:
         wsb = self.ws_bytes()
         ws = B.out((wsb,), torch.uint8, "workspace")
         if k == 3:
-            _call("asr_conv_backward", mode, _p(dy), _p(x), _p(mask), _p(w), _p(tdst), self.pm.n_theta, H_STEP, GAMMA,
-                  N, H, W, C, self.dt, _p(dx), _p(dth), _p(db), _p(dw), _p(ws), wsb, _stream())
+            B.call("asr_conv_backward", mode, _p(dy), _p(x), _p(mask), _p(w), _p(tdst), self.pm.n_theta, H_STEP, GAMMA,
+                   N, H, W, C, self.dt, _p(dx), _p(dth), _p(db), _p(dw), _p(ws), wsb, _stream())
         else:
-            _call("asr_conv_backward_k_bf16" if self.bf else "asr_conv_backward_k", mode, k, _p(dy), _p(x), _p(mask),
-                  _p(w), _p(tdst), self.pm.n_theta, H_STEP, GAMMA, N, H, W, C, _p(dx), _p(dth), _p(db), _p(dw), _p(ws),
-                  wsb, _stream())
+            B.call("asr_conv_backward_k_bf16" if self.bf else "asr_conv_backward_k", mode, k, _p(dy), _p(x), _p(mask),
+                   _p(w), _p(tdst), self.pm.n_theta, H_STEP, GAMMA, N, H, W, C, _p(dx), _p(dth), _p(db), _p(dw), _p(ws),
+                   wsb, _stream())
         return {"dx": dx, "dtheta": dth, "dbias": db, "dw": dw}
 
 
-def _conv_case(rt, case):
-    if case[0] not in _CONV_DATA:
-        _CONV_DATA[case[0]] = ConvCase(rt, *case)
-    return _CONV_DATA[case[0]]
+def _conv_case(rt, case, salt=None):
+    if (case[0], salt) not in _CONV_DATA:
+        _CONV_DATA[case[0], salt] = ConvCase(rt, *case, salt=salt)
+    return _CONV_DATA[case[0], salt]
 
 
 @pytest.mark.parametrize("mode_name", ["euler", "conv"])
@@ -297,12 +316,13 @@ RK2_IDS = [f"{d}-{'x'.join(map(str, s))}" for d, s in RK2]
 _RK2_DATA = {}
 
 
-def _rk2_case(rt, dtype, shape):
-    key = (dtype, shape)
+def _rk2_case(rt, dtype, shape, salt=None):
+    """With a salt: an independent draw, nothing computed from it (x_mid random values, the masks random bits)."""
+    key = (dtype, shape, salt)
     if key not in _RK2_DATA:
         N, H, W, C = shape
         bf = dtype == "bf16"
-        rng = np.random.default_rng(C * 100 + H)
+        rng = _rng(C * 100 + H, salt)
         d = dict(bf=bf, dt=rt.ASR_BF16 if bf else rt.ASR_F32, pm=rt.param_map(C))
         d["tdt"] = rt.torch_dtype(d["dt"])
         d["w"] = rt.theta_to_w(_dev(_theta3(C, rng)), C, d["pm"], GAMMA, d["dt"])
@@ -310,12 +330,25 @@ def _rk2_case(rt, dtype, shape):
         d["dy"] = _dev(rng.standard_normal(shape).astype(np.float32), bf)
         d["bias"] = _dev((rng.standard_normal(C) * 0.1).astype(np.float32))
         d["mb"] = rt.mask_bytes(N, H, W, C)
+        _RK2_DATA[key] = d
+        if salt is not None:
+            d["fwd"] = {"xmid": _dev(rng.standard_normal(shape).astype(np.float32), bf),
+                        "mask1": _rand_bytes(rng, d["mb"]), "mask2": _rand_bytes(rng, d["mb"])}
+            return d
         y, xm, m1, m2 = rt.rk2_forward(d["x"], d["w"], d["bias"], H_STEP)
         d["fwd"] = {"y": y, "xmid": xm, "mask1": m1, "mask2": m2}
         dx, dth, db, dw = rt.rk2_backward(d["dy"], d["x"], xm, m1, m2, d["w"], d["pm"], H_STEP, GAMMA, want_dw=True)
         d["bwd"] = {"dx": dx, "dtheta": dth, "dbias": db, "dw": dw}
-        _RK2_DATA[key] = d
     return _RK2_DATA[key]
+
+
+def _rk2_forward(B, d, shape):
+    N, H, W, C = shape
+    x, w, b = B.inp(d["x"], "x"), B.inp(d["w"], "w"), B.inp(d["bias"], "bias")
+    xm, y = B.out(shape, d["tdt"], "xmid"), B.out(shape, d["tdt"], "y")
+    m1, m2 = B.out((d["mb"],), torch.uint8, "mask1"), B.out((d["mb"],), torch.uint8, "mask2")
+    B.call("asr_rk2_forward", _p(x), _p(xm), _p(y), _p(m1), _p(m2), _p(w), _p(b), H_STEP, N, H, W, C, d["dt"], _stream())
+    return {"y": y, "xmid": xm, "mask1": m1, "mask2": m2}
 
 
 def _rk2_backward(B, d, shape, outs=("dx", "dtheta", "dbias", "dw")):
@@ -330,25 +363,15 @@ def _rk2_backward(B, d, shape, outs=("dx", "dtheta", "dbias", "dw")):
     dw = B.out((3, 3, C, C), torch.float32, "dw") if "dw" in outs else None
     wsb = int(_lib_().asr_rk2_backward_workspace_bytes(N, H, W, C, d["dt"]))
     ws = B.out((wsb,), torch.uint8, "workspace")
-    _call("asr_rk2_backward", _p(dy), _p(x), _p(xm), _p(m1), _p(m2), _p(w), _p(tdst), pm.n_theta, H_STEP, GAMMA, N, H,
-          W, C, d["dt"], _p(dx), _p(dth), _p(db), _p(dw), _p(ws), wsb, _stream())
+    B.call("asr_rk2_backward", _p(dy), _p(x), _p(xm), _p(m1), _p(m2), _p(w), _p(tdst), pm.n_theta, H_STEP, GAMMA, N, H,
+           W, C, d["dt"], _p(dx), _p(dth), _p(db), _p(dw), _p(ws), wsb, _stream())
     return {"dx": dx, "dtheta": dth, "dbias": db, "dw": dw}
 
 
 @pytest.mark.parametrize("dtype,shape", RK2, ids=RK2_IDS)
 def test_rk2_forward(rt, dtype, shape):
     d = _rk2_case(rt, dtype, shape)
-    N, H, W, C = shape
-
-    def launch(B):
-        x, w, b = B.inp(d["x"], "x"), B.inp(d["w"], "w"), B.inp(d["bias"], "bias")
-        xm, y = B.out(shape, d["tdt"], "xmid"), B.out(shape, d["tdt"], "y")
-        m1, m2 = B.out((d["mb"],), torch.uint8, "mask1"), B.out((d["mb"],), torch.uint8, "mask2")
-        _call("asr_rk2_forward", _p(x), _p(xm), _p(y), _p(m1), _p(m2), _p(w), _p(b), H_STEP, N, H, W, C, d["dt"],
-              _stream())
-        return {"y": y, "xmid": xm, "mask1": m1, "mask2": m2}
-
-    _both(launch, d["fwd"])
+    _both(lambda B: _rk2_forward(B, d, shape), d["fwd"])
 
 
 @pytest.mark.parametrize("dtype,shape", RK2, ids=RK2_IDS)
@@ -382,12 +405,14 @@ STACKS = [
 _STACK_DATA = {}
 
 
-def _stack_case(rt, name):
-    if name not in _STACK_DATA:
+def _stack_case(rt, name, salt=None):
+    """With a salt: an independent draw, nothing computed from it (the blocks' inputs random values, the masks
+    random bits)."""
+    if (name, salt) not in _STACK_DATA:
         _, dtype, shape, L = next(s for s in STACKS if s[0] == name)
         N, H, W, C = shape
         bf = dtype == "bf16"
-        rng = np.random.default_rng(1000 * C + 10 * N + L)
+        rng = _rng(1000 * C + 10 * N + L, salt)
         d = dict(shape=shape, L=L, bf=bf, dt=rt.ASR_BF16 if bf else rt.ASR_F32, pm=rt.param_map(C))
         d["tdt"] = rt.torch_dtype(d["dt"])
         d["w"] = rt.theta_to_w(_dev(_theta3(C, rng, L)), C, d["pm"], GAMMA, d["dt"], layers=L).reshape(L, -1)
@@ -395,13 +420,17 @@ def _stack_case(rt, name):
         d["x0"] = _dev(rng.standard_normal(shape).astype(np.float32), bf)
         d["dyL"] = _dev((rng.standard_normal(shape) * 0.1).astype(np.float32), bf)
         d["P"], d["mb"], d["per"] = N * H * W * C, rt.mask_bytes(N, H, W, C), d["w"][0].numel()
+        _STACK_DATA[name, salt] = d
+        if salt is not None:
+            d["xs"] = _dev(rng.standard_normal((L,) + shape).astype(np.float32), bf)
+            d["masks"] = _rand_bytes(rng, L, d["mb"])
+            return d
         ys, masks = rt.block_stack_forward(d["x0"], d["w"], d["bias"], H_STEP)
         d["ys"], d["masks"] = ys, masks
         d["xs"] = torch.cat([d["x0"].unsqueeze(0), ys[:L - 1]]).contiguous()
         dx0, dp = rt.block_stack_backward(d["dyL"], d["x0"], ys, masks, d["w"], d["pm"], H_STEP, GAMMA)
         d["dx0"], d["dp"] = dx0, dp
-        _STACK_DATA[name] = d
-    return _STACK_DATA[name]
+    return _STACK_DATA[name, salt]
 
 
 def _strided(t, L, per, stride):
@@ -433,8 +462,8 @@ def _stack_forward(B, d, ys_extra=0, mask_extra=0, bias_extra=0):
     bias = B.inp(_strided(d["bias"], L, C, bstr), "bias")
     ys = B.out(((L - 1) * ystr + P,), d["tdt"], "ys")
     masks = B.out(((L - 1) * mstr + mb,), torch.uint8, "masks")
-    _call("asr_block_stack_forward", _p(x0), _p(ys), ystr, _p(masks), mstr, _p(w), per, _p(bias), bstr, H_STEP, N, H, W,
-          C, L, d["dt"], 1, _stream())
+    B.call("asr_block_stack_forward", _p(x0), _p(ys), ystr, _p(masks), mstr, _p(w), per, _p(bias), bstr, H_STEP, N, H, W,
+           C, L, d["dt"], 1, _stream())
     return ys, masks, ystr, mstr
 
 
@@ -450,8 +479,8 @@ def _stack_backward(B, d, x_extra=0, want_dparams=True):
     dx0 = B.out(d["shape"], d["tdt"], "dx0")
     dp = B.out((L, pm.n_theta + C), torch.float32, "dparams") if want_dparams else None
     ws = B.out((wsb,), torch.uint8, "workspace")
-    _call("asr_block_stack_backward", _p(dyL), _p(xs), xstr, _p(masks), mb, _p(w), per, _p(tdst), pm.n_theta, H_STEP,
-          GAMMA, N, H, W, C, L, d["dt"], _p(dx0), _p(dp), _p(ws), wsb, _stream())
+    B.call("asr_block_stack_backward", _p(dyL), _p(xs), xstr, _p(masks), mb, _p(w), per, _p(tdst), pm.n_theta, H_STEP,
+           GAMMA, N, H, W, C, L, d["dt"], _p(dx0), _p(dp), _p(ws), wsb, _stream())
     return {"dx0": dx0, "dparams": dp}
 
 
@@ -505,130 +534,165 @@ def test_block_stack_backward_strided(rt, name):
 _RK2S = {}
 
 
-def _rk2_stack_case(rt):
-    if not _RK2S:
+def _rk2_stack_case(rt, salt=None):
+    """With a salt: an independent draw, nothing computed from it (as _stack_case)."""
+    if salt not in _RK2S:
         N, H, W, C, L = 2, 16, 32, 64, 2
         shape = (N, H, W, C)
-        rng = np.random.default_rng(N * 5 + L)
-        d = _RK2S
+        rng = _rng(N * 5 + L, salt)
+        d = _RK2S[salt] = {}
         d.update(shape=shape, L=L, pm=rt.param_map(C), P=N * H * W * C, mb=rt.mask_bytes(N, H, W, C))
         d["w"] = rt.theta_to_w(_dev(_theta3(C, rng, L)), C, d["pm"], GAMMA, rt.ASR_BF16, layers=L).reshape(L, -1)
         d["bias"] = _dev((rng.standard_normal((L, C)) * 0.1).astype(np.float32))
         d["x0"] = _dev(rng.standard_normal(shape).astype(np.float32), True)
         d["dyL"] = _dev((rng.standard_normal(shape) * 0.1).astype(np.float32), True)
+        if salt is not None:
+            d["xs"] = _dev(rng.standard_normal((L,) + shape).astype(np.float32), True)
+            d["xm"] = _dev(rng.standard_normal((L,) + shape).astype(np.float32), True)
+            d["m1"], d["m2"] = _rand_bytes(rng, L, d["mb"]), _rand_bytes(rng, L, d["mb"])
+            return d
         d["ys"], d["xm"], d["m1"], d["m2"] = rt.rk2_stack_forward(d["x0"], d["w"], d["bias"], H_STEP)
+        d["xs"] = torch.cat([d["x0"].unsqueeze(0), d["ys"][:L - 1]]).contiguous()
         d["dx0"], d["dp"] = rt.rk2_stack_backward(d["dyL"], d["x0"], d["ys"], d["xm"], d["m1"], d["m2"], d["w"], d["pm"],
                                                   H_STEP, GAMMA)
-    return _RK2S
+    return _RK2S[salt]
+
+
+def _rk2_stack_forward(B, rt, d):
+    N, H, W, C = d["shape"]
+    L, P, mb = d["L"], d["P"], d["mb"]
+    x0, w, bias = B.inp(d["x0"], "x0"), B.inp(d["w"], "w"), B.inp(d["bias"], "bias")
+    ys, xm = B.out((L,) + d["shape"], torch.bfloat16, "ys"), B.out((L,) + d["shape"], torch.bfloat16, "xmids")
+    m1, m2 = B.out((L, mb), torch.uint8, "masks1"), B.out((L, mb), torch.uint8, "masks2")
+    B.call("asr_rk2_stack_forward", _p(x0), _p(ys), _p(xm), P, _p(m1), _p(m2), mb, _p(w), d["w"][0].numel(), _p(bias),
+           C, H_STEP, N, H, W, C, L, rt.ASR_BF16, _stream())
+    return {"ys": ys, "xmids": xm, "masks1": m1, "masks2": m2}
+
+
+def _rk2_stack_backward(B, rt, d):
+    N, H, W, C = d["shape"]
+    L, P, mb, pm = d["L"], d["P"], d["mb"], d["pm"]
+    dyL, xs, xm = B.inp(d["dyL"], "dyL"), B.inp(d["xs"], "xs"), B.inp(d["xm"], "xmids")
+    m1, m2, w = B.inp(d["m1"], "masks1"), B.inp(d["m2"], "masks2"), B.inp(d["w"], "w")
+    tdst = B.inp(pm.device(dyL.device)[1], "theta_dst")
+    wsb = int(_lib_().asr_rk2_stack_backward_workspace_bytes(N, H, W, C, L, rt.ASR_BF16))
+    dx0, dp = B.out(d["shape"], torch.bfloat16, "dx0"), B.out((L, pm.n_theta + C), torch.float32, "dparams")
+    ws = B.out((wsb,), torch.uint8, "workspace")
+    B.call("asr_rk2_stack_backward", _p(dyL), _p(xs), _p(xm), P, _p(m1), _p(m2), mb, _p(w), d["w"][0].numel(),
+           _p(tdst), pm.n_theta, H_STEP, GAMMA, N, H, W, C, L, rt.ASR_BF16, _p(dx0), _p(dp), _p(ws), wsb, _stream())
+    return {"dx0": dx0, "dparams": dp}
 
 
 def test_rk2_stack_forward(rt):
     d = _rk2_stack_case(rt)
-    N, H, W, C = d["shape"]
-    L, P, mb = d["L"], d["P"], d["mb"]
-
-    def launch(B):
-        x0, w, bias = B.inp(d["x0"], "x0"), B.inp(d["w"], "w"), B.inp(d["bias"], "bias")
-        ys, xm = B.out((L,) + d["shape"], torch.bfloat16, "ys"), B.out((L,) + d["shape"], torch.bfloat16, "xmids")
-        m1, m2 = B.out((L, mb), torch.uint8, "masks1"), B.out((L, mb), torch.uint8, "masks2")
-        _call("asr_rk2_stack_forward", _p(x0), _p(ys), _p(xm), P, _p(m1), _p(m2), mb, _p(w), d["w"][0].numel(), _p(bias),
-              C, H_STEP, N, H, W, C, L, rt.ASR_BF16, _stream())
-        return {"ys": ys, "xmids": xm, "masks1": m1, "masks2": m2}
-
-    _both(launch, {"ys": d["ys"], "xmids": d["xm"], "masks1": d["m1"], "masks2": d["m2"]})
+    _both(lambda B: _rk2_stack_forward(B, rt, d), {"ys": d["ys"], "xmids": d["xm"], "masks1": d["m1"], "masks2": d["m2"]})
 
 
 def test_rk2_stack_backward(rt):
     d = _rk2_stack_case(rt)
-    N, H, W, C = d["shape"]
-    L, P, mb, pm = d["L"], d["P"], d["mb"], d["pm"]
-    xs_t = torch.cat([d["x0"].unsqueeze(0), d["ys"][:L - 1]]).contiguous()
-
-    def launch(B):
-        dyL, xs, xm = B.inp(d["dyL"], "dyL"), B.inp(xs_t, "xs"), B.inp(d["xm"], "xmids")
-        m1, m2, w = B.inp(d["m1"], "masks1"), B.inp(d["m2"], "masks2"), B.inp(d["w"], "w")
-        tdst = B.inp(pm.device(dyL.device)[1], "theta_dst")
-        wsb = int(_lib_().asr_rk2_stack_backward_workspace_bytes(N, H, W, C, L, rt.ASR_BF16))
-        dx0, dp = B.out(d["shape"], torch.bfloat16, "dx0"), B.out((L, pm.n_theta + C), torch.float32, "dparams")
-        ws = B.out((wsb,), torch.uint8, "workspace")
-        _call("asr_rk2_stack_backward", _p(dyL), _p(xs), _p(xm), P, _p(m1), _p(m2), mb, _p(w), d["w"][0].numel(),
-              _p(tdst), pm.n_theta, H_STEP, GAMMA, N, H, W, C, L, rt.ASR_BF16, _p(dx0), _p(dp), _p(ws), wsb, _stream())
-        return {"dx0": dx0, "dparams": dp}
-
-    _both(launch, {"dx0": d["dx0"], "dparams": d["dp"]})
+    _both(lambda B: _rk2_stack_backward(B, rt, d), {"dx0": d["dx0"], "dparams": d["dp"]})
 
 
 # ---------------------------------------------------------------------------
 # Transitions (fp32, stride 2: TF's asymmetric padding)
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("N,H,W,Ci,Co", [(2, 7, 9, 5, 6), (2, 16, 16, 32, 64), (1, 8, 8, 64, 128)])
+def _transition_case(rt, dims, S=2, salt=None):
+    """Operands of one transition and, without a salt, the wrapper's results (with one: an independent draw,
+    nothing computed from it, the mask's bytes random 0 / 1)."""
+    N, H, W, Ci, Co = dims
+    rng = _rng(N * 100 + H + Ci, salt)  # test_gpu_stages.test_transition_vs_oracle
+    d = dict(dims=dims, S=S, out_shape=(N, -(-H // S), -(-W // S), Co))
+    d["x"] = _dev(rng.standard_normal((N, H, W, Ci)).astype(np.float32))
+    d["k2"] = _dev((rng.standard_normal((3, 3, Ci, Co)) * np.sqrt(2 / (9 * Ci))).astype(np.float32))
+    d["k1"] = _dev((rng.standard_normal((1, 1, Ci, Co)) * np.sqrt(2 / Ci)).astype(np.float32))
+    d["b2"] = _dev((rng.standard_normal(Co) * 0.1).astype(np.float32))
+    d["b1"] = _dev((rng.standard_normal(Co) * 0.1).astype(np.float32))
+    d["dy"] = _dev(rng.standard_normal(d["out_shape"]).astype(np.float32))
+    if salt is not None:
+        d["mask"] = _rand_bytes(rng, *d["out_shape"], below=2)
+        return d
+    d["y"], d["mask"] = rt.transition_forward(d["x"], d["k2"], d["b2"], d["k1"], d["b1"], S)
+    d["dx"], d["dparams"] = rt.transition_backward(d["dy"], d["x"], d["mask"], d["k2"], d["k1"], S)
+    return d
+
+
+def _transition_forward(B, d):
+    N, H, W, Ci, Co = d["dims"]
+    xi, k2i, b2i, k1i, b1i = (B.inp(d[n], n) for n in ("x", "k2", "b2", "k1", "b1"))
+    y, mask = B.out(d["out_shape"], torch.float32, "y"), B.out(d["out_shape"], torch.uint8, "mask")
+    B.call("asr_transition_forward", _p(xi), _p(y), _p(mask), _p(k2i), _p(b2i), _p(k1i), _p(b1i), N, H, W, Ci, Co, d["S"],
+           _stream())
+    return {"y": y, "mask": mask}
+
+
+def _transition_backward(B, d):
+    N, H, W, Ci, Co = d["dims"]
+    dyi, xi, mi, k2i, k1i = (B.inp(d[n], n) for n in ("dy", "x", "mask", "k2", "k1"))
+    dx = B.out((N, H, W, Ci), torch.float32, "dx")
+    dp = B.out((9 * Ci * Co + Co + Ci * Co + Co,), torch.float32, "dparams")
+    nb = int(_lib_().asr_transition_backward_workspace_bytes(N, H, W, Ci, Co, d["S"]))
+    ws = B.out((max(nb, 1),), torch.uint8, "workspace")
+    B.call("asr_transition_backward", _p(dyi), _p(xi), _p(mi), _p(k2i), _p(k1i), N, H, W, Ci, Co, d["S"], _p(dx), _p(dp),
+           _p(ws), nb, _stream())
+    return {"dx": dx, "dparams": dp}
+
+
+TRANSITIONS = [(2, 7, 9, 5, 6), (2, 16, 16, 32, 64), (1, 8, 8, 64, 128)]
+
+
+@pytest.mark.parametrize("N,H,W,Ci,Co", TRANSITIONS)
 def test_transition(rt, N, H, W, Ci, Co):
-    S = 2
-    rng = np.random.default_rng(N * 100 + H + Ci)  # test_gpu_stages.test_transition_vs_oracle
-    x = _dev(rng.standard_normal((N, H, W, Ci)).astype(np.float32))
-    k2 = _dev((rng.standard_normal((3, 3, Ci, Co)) * np.sqrt(2 / (9 * Ci))).astype(np.float32))
-    k1 = _dev((rng.standard_normal((1, 1, Ci, Co)) * np.sqrt(2 / Ci)).astype(np.float32))
-    b2 = _dev((rng.standard_normal(Co) * 0.1).astype(np.float32))
-    b1 = _dev((rng.standard_normal(Co) * 0.1).astype(np.float32))
-    Ho, Wo = -(-H // S), -(-W // S)
-    dy = _dev(rng.standard_normal((N, Ho, Wo, Co)).astype(np.float32))
-    y_want, mask_want = rt.transition_forward(x, k2, b2, k1, b1, S)
-    dx_want, dp_want = rt.transition_backward(dy, x, mask_want, k2, k1, S)
-
-    def fwd(B):
-        xi, k2i, b2i, k1i, b1i = (B.inp(t, n) for t, n in ((x, "x"), (k2, "k2"), (b2, "b2"), (k1, "k1"), (b1, "b1")))
-        y, mask = B.out((N, Ho, Wo, Co), torch.float32, "y"), B.out((N, Ho, Wo, Co), torch.uint8, "mask")
-        _call("asr_transition_forward", _p(xi), _p(y), _p(mask), _p(k2i), _p(b2i), _p(k1i), _p(b1i), N, H, W, Ci, Co, S,
-              _stream())
-        return {"y": y, "mask": mask}
-
-    _both(fwd, {"y": y_want, "mask": mask_want})
-
-    def bwd(B):
-        dyi, xi, mi, k2i, k1i = (B.inp(t, n) for t, n in ((dy, "dy"), (x, "x"), (mask_want, "mask"), (k2, "k2"),
-                                                          (k1, "k1")))
-        dx = B.out((N, H, W, Ci), torch.float32, "dx")
-        dp = B.out((9 * Ci * Co + Co + Ci * Co + Co,), torch.float32, "dparams")
-        nb = int(_lib_().asr_transition_backward_workspace_bytes(N, H, W, Ci, Co, S))
-        ws = B.out((max(nb, 1),), torch.uint8, "workspace")
-        _call("asr_transition_backward", _p(dyi), _p(xi), _p(mi), _p(k2i), _p(k1i), N, H, W, Ci, Co, S, _p(dx), _p(dp),
-              _p(ws), nb, _stream())
-        return {"dx": dx, "dparams": dp}
-
-    _both(bwd, {"dx": dx_want, "dparams": dp_want})
+    d = _transition_case(rt, (N, H, W, Ci, Co))
+    _both(lambda B: _transition_forward(B, d), {"y": d["y"], "mask": d["mask"]})
+    _both(lambda B: _transition_backward(B, d), {"dx": d["dx"], "dparams": d["dparams"]})
 
 
 # ---------------------------------------------------------------------------
 # asr_theta_to_w, _k, _k_bf16 with layer strides
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("name,bf,k,C", [("f32-hwio", False, 3, 5), ("bf16-balanced-c64", True, 3, 64),
-                                         ("bf16-nearest-c128", True, 3, 128), ("f32-k5", False, 5, 3),
-                                         ("bf16-k5-pack", True, 5, 16)])
-def test_theta_to_w_strided(rt, name, bf, k, C):
-    """L = 2, w_stride = per-layer elements + 64, theta_stride = n_theta + C + 3 (the gap between the
-    thetas NaN): each layer equals the naturally strided run's, the gap in w keeps its prefill."""
+THETA = [("f32-hwio", False, 3, 5), ("bf16-balanced-c64", True, 3, 64), ("bf16-nearest-c128", True, 3, 128),
+         ("f32-k5", False, 5, 3), ("bf16-k5-pack", True, 5, 16)]
+
+
+def _theta_case(rt, bf, k, C, salt=None):
+    """L = 2 strided thetas (the gap NaN) and the strides; `salt`: an independent draw."""
     L = 2
     dt = rt.ASR_BF16 if bf else rt.ASR_F32
     pm = rt.param_map(C) if k == 3 else rt.param_map(C, rt.ASR_PARAM_GENERAL, True, k)
     nt = pm.n_theta
-    rng = np.random.default_rng(C + k)
+    rng = _rng(C + k, salt)
     th = _theta3(C, rng, L) if k == 3 else (0.2 * rng.standard_normal(L * nt)).astype(np.float32)
     th = _dev(th).reshape(L, nt)
-    want = rt.theta_to_w(th.reshape(-1), C, pm, GAMMA, dt, layers=L).reshape(L, -1)
-    per = want[0].numel()
+    per = (rt.wpack_elems(C) if k == 3 else rt.wpack_elems_k(C, k)) if bf else k * k * C * C
     tstr, wstr = nt + C + 3, per + 64
-    theta = _strided(th, L, nt, tstr)
-    w_src = pm.device(th.device)[0]
+    return dict(L=L, C=C, k=k, bf=bf, dt=dt, pm=pm, th=th, per=per, tstr=tstr, wstr=wstr,
+                theta=_strided(th, L, nt, tstr), w_src=pm.device(th.device)[0])
+
+
+def _theta_to_w(B, d):
+    L, C, k, per, tstr, wstr = d["L"], d["C"], d["k"], d["per"], d["tstr"], d["wstr"]
+    t_in, src = B.inp(d["theta"], "theta"), B.inp(d["w_src"], "w_src")
+    w = B.out(((L - 1) * wstr + per,), torch.bfloat16 if d["bf"] else torch.float32, "w_out")
+    if k == 3:
+        B.call("asr_theta_to_w", _p(t_in), tstr, L, C, _p(src), GAMMA, _p(w), wstr, d["dt"], _stream())
+    else:
+        B.call("asr_theta_to_w_k_bf16" if d["bf"] else "asr_theta_to_w_k", _p(t_in), tstr, L, C, k, _p(src), GAMMA, _p(w),
+               wstr, _stream())
+    return {"w_out": w}
+
+
+@pytest.mark.parametrize("name,bf,k,C", THETA)
+def test_theta_to_w_strided(rt, name, bf, k, C):
+    """L = 2, w_stride = per-layer elements + 64, theta_stride = n_theta + C + 3 (the gap between the
+    thetas NaN): each layer equals the naturally strided run's, the gap in w keeps its prefill."""
+    d = _theta_case(rt, bf, k, C)
+    L, per, wstr = d["L"], d["per"], d["wstr"]
+    want = rt.theta_to_w(d["th"].reshape(-1), C, d["pm"], GAMMA, d["dt"], layers=L).reshape(L, -1)
+    assert want[0].numel() == per and want.dtype == (torch.bfloat16 if bf else torch.float32)
     got = []
     for fill in PREFILLS:
         B = Bufs(fill)
-        t_in, src = B.inp(theta, "theta"), B.inp(w_src, "w_src")
-        w = B.out(((L - 1) * wstr + per,), want.dtype, "w_out")
-        if k == 3:
-            _call("asr_theta_to_w", _p(t_in), tstr, L, C, _p(src), GAMMA, _p(w), wstr, dt, _stream())
-        else:
-            _call("asr_theta_to_w_k_bf16" if bf else "asr_theta_to_w_k", _p(t_in), tstr, L, C, k, _p(src), GAMMA, _p(w),
-                  wstr, _stream())
+        w = _theta_to_w(B, d)["w_out"]
         B.check()
         _gaps_keep(w, L, per, wstr, fill, "w_out")
         got.append({"w": _rows(w, L, per, wstr)})
@@ -652,6 +716,18 @@ def _opt_data(n, slots, seed):
     return p, grads, state
 
 
+def _optimizer_update(B, cfg, p, grads, state):
+    pi, gi, si = B.inp(p, "params"), B.inp(grads, "grads"), B.inp(state, "state")
+    B.call("asr_optimizer_update", ct.byref(cfg), _p(pi), _p(gi), _p(si), p.numel(), _stream())
+    return {"params": pi, "state": si}
+
+
+def _adam_update(B, p, grads, m, v, hp):
+    pi, gi, mi, vi = B.inp(p, "params"), B.inp(grads, "grads"), B.inp(m, "m"), B.inp(v, "v")
+    B.call("asr_adam_update", _p(pi), _p(gi), _p(mi), _p(vi), p.numel(), *hp, _stream())
+    return {"params": pi, "m": mi, "v": vi}
+
+
 @pytest.mark.parametrize("n", OPT_SIZES)
 @pytest.mark.parametrize("name,kind,flags,lr,a,b,eps", OPT, ids=[o[0] for o in OPT])
 def test_optimizer_update(rt, name, kind, flags, lr, a, b, eps, n):
@@ -665,12 +741,11 @@ def test_optimizer_update(rt, name, kind, flags, lr, a, b, eps, n):
     p_want, s_want = p.clone(), state.clone()
     rt.optimizer_update(cfg, p_want, grads, s_want)
     B = Bufs(0xFF)
-    pi, gi, si = B.inp(p, "params"), B.inp(grads, "grads"), B.inp(state, "state")
-    assert si.numel() == slots * n
-    _call("asr_optimizer_update", ct.byref(cfg), _p(pi), _p(gi), _p(si), n, _stream())
+    got = _optimizer_update(B, cfg, p, grads, state)
+    assert got["state"].numel() == slots * n
     B.check()
-    _equal_wrapper({"params": pi, "state": si}, {"params": p_want, "state": s_want})
-    assert not _same(pi, p)
+    _equal_wrapper(got, {"params": p_want, "state": s_want})
+    assert not _same(got["params"], p)
 
 
 @pytest.mark.parametrize("n", OPT_SIZES)
@@ -681,82 +756,94 @@ def test_adam_update(rt, n):
     p_want, m_want, v_want = p.clone(), m.clone(), v.clone()
     rt.adam_update(p_want, grads, m_want, v_want, *hp)
     B = Bufs(0xFF)
-    pi, gi, mi, vi = B.inp(p, "params"), B.inp(grads, "grads"), B.inp(m, "m"), B.inp(v, "v")
-    _call("asr_adam_update", _p(pi), _p(gi), _p(mi), _p(vi), n, *hp, _stream())
+    got = _adam_update(B, p, grads, m, v, hp)
     B.check()
-    _equal_wrapper({"params": pi, "m": mi, "v": vi}, {"params": p_want, "m": m_want, "v": v_want})
-    assert not _same(pi, p)
+    _equal_wrapper(got, {"params": p_want, "m": m_want, "v": v_want})
+    assert not _same(got["params"], p)
 
 
 # ---------------------------------------------------------------------------
 # The augmentation launch
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["crop_flip_u8_n1", "pad_height_u8"])
-def test_augment_batch(rt, name):
-    """The smallest cropping plan with uint8 output and the smallest cropping + padding plan (float32
-    output, whose zero border the kernel writes itself) of tests/test_augment_gpu.py."""
+AUGMENT = ["crop_flip_u8_n1", "pad_height_u8"]
+
+
+def _augment_case(name, salt=None):
+    """The plan, its config and item table, and the source images (`salt`: other random images, the same table)."""
     from differential_equations_resnet_amd import _lib
     _, src, plan, table, _ = next(c for c in A.cases() if c[0] == name)
-    feats = torch.from_numpy(src).cuda()
-    items = torch.from_numpy(table.view(np.uint8).copy()).cuda()
-    want = rt.augment_batch(feats, plan, items)
-    N = len(table)
+    if salt is not None:
+        src = _rng(len(name), salt).integers(0, 256, src.shape, dtype=src.dtype)
     Hs, Ws, C = plan.in_shape
     Ho, Wo, _ = plan.out_shape
     out_u8 = np.dtype(plan.out_dtype) == np.uint8
-    assert out_u8 == (name == "crop_flip_u8_n1") and want.dtype == (torch.uint8 if out_u8 else torch.float32)
     color = list(plan.color) + [_lib.ASR_AUG_NONE] * (2 - len(plan.color))
     cfg = _lib.AugPlanConfig(Hs, Ws, C, _lib.ASR_U8, Ho, Wo, _lib.ASR_U8 if out_u8 else _lib.ASR_F32, int(plan.resize),
                              int(plan.resized[0]), int(plan.resized[1]), int(plan.pad[0]), int(plan.pad[1]),
                              int(bool(plan.flip_src)), (ct.c_int * 2)(*color))
+    return dict(plan=plan, cfg=cfg, N=len(table), out_shape=(len(table), Ho, Wo, C),
+                out_dtype=torch.uint8 if out_u8 else torch.float32, feats=torch.from_numpy(src).cuda(),
+                items=torch.from_numpy(table.view(np.uint8).copy()).cuda())
 
-    def launch(B):
-        f, it = B.inp(feats, "src"), B.inp(items, "items")
-        out = B.out((N, Ho, Wo, C), want.dtype, "out")
-        _call("asr_augment_batch", _p(f), int(feats.shape[0]), ct.byref(cfg), _p(it), N, _p(out), _stream())
-        return {"out": out}
 
-    _both(launch, {"out": want})
+def _augment_batch(B, d):
+    f, it = B.inp(d["feats"], "src"), B.inp(d["items"], "items")
+    out = B.out(d["out_shape"], d["out_dtype"], "out")
+    B.call("asr_augment_batch", _p(f), int(d["feats"].shape[0]), ct.byref(d["cfg"]), _p(it), d["N"], _p(out), _stream())
+    return {"out": out}
+
+
+@pytest.mark.parametrize("name", AUGMENT)
+def test_augment_batch(rt, name):
+    """The smallest cropping plan with uint8 output and the smallest cropping + padding plan (float32
+    output, whose zero border the kernel writes itself) of tests/test_augment_gpu.py."""
+    d = _augment_case(name)
+    want = rt.augment_batch(d["feats"], d["plan"], d["items"])
+    assert (d["out_dtype"] == torch.uint8) == (name == "crop_flip_u8_n1") and want.dtype == d["out_dtype"]
+    _both(lambda B: _augment_batch(B, d), {"out": want})
 
 
 # ---------------------------------------------------------------------------
 # The executors' workspaces
 # ---------------------------------------------------------------------------
-def _net_executor(rt, dtype, N, H, W, C, L, k=3, integrator="euler", inference=False):
+def _net_executor(rt, dtype, N, H, W, C, L, k=3, integrator="euler", inference=False, salt=None):
+    """(executor, params, the generator for images and targets, its prepare call); `salt`: independent draws."""
     kw = dict(param_kind=rt.ASR_PARAM_GENERAL, kernel_size=k) if k != 3 else {}
     ex = rt.NetExecutor(N, H, W, 3, C, L, 10, H_STEP, GAMMA, subtract_mean=127.5, divide_by_stddev=127.5, dtype=dtype,
                         integrator=integrator, inference=inference, **kw)
-    rng = np.random.default_rng(C + L + k)
+    rng = _rng(C + L + k, salt)
     if k == 3:
         from differential_equations_resnet_amd.netparams import init_net_params
-        params = init_net_params(C, L, 3, 10, seed=5, bias_std=0.05)
+        params = init_net_params(C, L, 3, 10, seed=5 if salt is None else 1000 + salt, bias_std=0.05)
     else:
         spec = KO.KNetSpec(C=C, L=L, h=H_STEP, gamma=GAMMA, H=H, W=W, kind="general", k1=3, kb=k)
         params = O.flatten(KO.init_params(spec, rng))
     return ex, _dev(np.asarray(params, np.float32)), rng, "asr_net_prepare"
 
 
-def _stages_executor(rt, dtype):
+def _stages_executor(rt, dtype, salt=None):
     stages = [(16, 1, 0), (32, 1, 2), (64, 1, 2)]
     ex = rt.StagesExecutor(2, 32, 32, 3, stages, 10, H_STEP, GAMMA, subtract_mean=127.5, divide_by_stddev=127.5,
                            dtype=dtype)
     spec = O.StagesSpec(stages=stages, h=H_STEP, gamma=GAMMA, H=32, W=32, kind="3by3", antisymmetric=True)
-    rng = np.random.default_rng(0)
+    rng = _rng(0, salt)
     params = O.stages_init_params(spec, rng, np.float64, bias_std=0.05)  # test_gpu_stages._stages_setup
     params[-2] = params[-2] * 0.05
     return ex, _dev(O.flatten(params).astype(np.float32)), rng, "asr_stages_prepare"
 
 
 EXECUTORS = {
-    "net-bf16-c16": lambda rt: _net_executor(rt, "bfloat16", 2, 32, 32, 16, 2),
-    "net-bf16-c64-euler": lambda rt: _net_executor(rt, "bfloat16", 2, 32, 32, 64, 2),
-    "net-bf16-c64-rk2": lambda rt: _net_executor(rt, "bfloat16", 2, 32, 32, 64, 2, integrator="rk2"),
-    "net-bf16-c128": lambda rt: _net_executor(rt, "bfloat16", 2, 8, 16, 128, 2),
-    "net-bf16-k5": lambda rt: _net_executor(rt, "bfloat16", 2, 16, 16, 16, 2, k=5),
-    "net-f32": lambda rt: _net_executor(rt, "float32", 2, 7, 9, 5, 2),
-    "stages-f32": lambda rt: _stages_executor(rt, "float32"),
-    "stages-bf16": lambda rt: _stages_executor(rt, "bfloat16"),
-    "net-bf16-c64-inference": lambda rt: _net_executor(rt, "bfloat16", 2, 32, 32, 64, 2, inference=True),
+    "net-bf16-c16": lambda rt, salt=None: _net_executor(rt, "bfloat16", 2, 32, 32, 16, 2, salt=salt),
+    "net-bf16-c64-euler": lambda rt, salt=None: _net_executor(rt, "bfloat16", 2, 32, 32, 64, 2, salt=salt),
+    "net-bf16-c64-rk2": lambda rt, salt=None: _net_executor(rt, "bfloat16", 2, 32, 32, 64, 2, integrator="rk2",
+                                                            salt=salt),
+    "net-bf16-c128": lambda rt, salt=None: _net_executor(rt, "bfloat16", 2, 8, 16, 128, 2, salt=salt),
+    "net-bf16-k5": lambda rt, salt=None: _net_executor(rt, "bfloat16", 2, 16, 16, 16, 2, k=5, salt=salt),
+    "net-f32": lambda rt, salt=None: _net_executor(rt, "float32", 2, 7, 9, 5, 2, salt=salt),
+    "stages-f32": lambda rt, salt=None: _stages_executor(rt, "float32", salt=salt),
+    "stages-bf16": lambda rt, salt=None: _stages_executor(rt, "bfloat16", salt=salt),
+    "net-bf16-c64-inference": lambda rt, salt=None: _net_executor(rt, "bfloat16", 2, 32, 32, 64, 2, inference=True,
+                                                                  salt=salt),
 }
 
 
