@@ -19,8 +19,8 @@ LIB = os.path.join(HERE, "libasr.so")
 # Every *.hip of csrc/ (tests/test_csrc_layout.py).  The one list: tests/test_isa.py and tools/build_variants.sh
 # read it here (this module imports the standard library only).
 SOURCES = ["asr_theta.hip", "asr_block_mfma.hip", "asr_conv_f32.hip", "asr_conv_bf16.hip", "asr_stage_img.hip",
-           "asr_conv_kxk.hip", "asr_stem_head.hip", "asr_api.hip", "asr_dist.hip", "asr_deep16.hip", "asr_stages.hip",
-           "asr_augment.hip", "asr_optim.hip"]
+           "asr_conv_kxk.hip", "asr_stem_head.hip", "asr_api.hip", "asr_net.hip", "asr_dist.hip", "asr_deep16.hip",
+           "asr_stages.hip", "asr_augment.hip", "asr_optim.hip"]
 ARCH = "gfx950"
 
 

@@ -47,6 +47,13 @@ struct WsCursor {
   }
 };
 
+// One conv application's backward workspace (bwd_ws_layout, asr_internal.h; asr_conv_backward's and
+// asr_rk2_backward's layout, and the per-block area of the network workspace): dz in fp32 (fp32 only),
+// the weight-gradient slabs, reduce_and_project's rows, RK2's inter-stage gradient g.
+struct BwdWs {
+  size_t dz, slabs, red, g, total;
+};
+
 // One launch of the balanced bf16 weight pack for several layer sets (the
 // multi-stage net's stages, asr_stages.hip): one workgroup per layer, so the
 // stages' packs run side by side (theta_to_w_bf16_jobs, asr_internal.h;

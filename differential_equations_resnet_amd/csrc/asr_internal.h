@@ -9,12 +9,13 @@
 
 namespace asr {
 
-// conv modes of the 3x3 block kernels (asr_conv_f32.hip: conv_f32's fmode, asr_api.hip's dispatch; asr_conv_bf16.hip)
+// conv modes of the 3x3 block kernels (asr_conv_f32.hip: conv_f32's fmode, the dispatch of asr_api.hip and
+// asr_net.hip; asr_conv_bf16.hip)
 enum { F_EULER = 0, F_CONV = 1, F_RELU = 2, B_EULER = 3, B_CONV = 4 };
 
 // Most weight-gradient slabs one launch writes: the grid bound of the block and
 // stack kernels and of stem_wgrad_mfma (asr_block_mfma.hip), and the slab rows
-// the workspaces reserve per block (asr_api.hip).
+// the workspaces reserve per block (asr_api.hip, asr_net.hip).
 constexpr int kMaxBlockSlabs = 512;
 // The name for code about the stem's weight gradient: stem_wgrad's grid bound
 // (asr_stem_head.hip), the stem slab rows of the multi-stage workspace
@@ -194,6 +195,8 @@ int head(const void* xL, int act_bf16, const float* fck, const float* fcb, const
          void* growL = nullptr);
 int head_param_grads(const float* gap, const float* dlogits, int N, int C, int K, float* dfck, float* dfcb,
                      const float* loss_per, float* loss_out, hipStream_t s);
+// dz1 = dx1 * [x1 > 0] in place (bf16, n % 8 == 0): the stem's relu' where block 0's backward did not fuse it
+int relu_grad_bf16(void* d, const void* x, long n, hipStream_t s);
 
 // ---- asr_augment.hip -------------------------------------------------------
 // the dataset preprocessors in one launch per batch (asr_augment_batch, asr.h, is this with a void* stream)
@@ -201,9 +204,25 @@ int augment_batch(const void* src, long n_src, const asr_aug_plan* plan, const a
                   hipStream_t s);
 
 // ---- asr_api.hip -----------------------------------------------------------
+// (the layer-level ABI's helpers that the executors, asr_net.hip and asr_stages.hip, call)
+bool mfma_supported(int C, int W);
+int check_shape(int N, int H, int W, int C);
+// BwdWs (asr_common.h) of one conv application (stages = 2: an RK2 block); slab_rows < 0: the rows its kernel may write
+BwdWs bwd_ws_layout(int N, int H, int W, int C, int dtype, int stages = 1, int K = 3, int slab_rows = -1);
+int block_backward(int mode, const void* dy, const void* x, const uint8_t* mask, const void* w, float h, float gamma,
+                   int N, int H, int W, int C, int dtype, void* dx, bool need_w, const void* extra, bool skip_dy,
+                   float* slabs, float* dz_scratch, int* nsl, hipStream_t s, bool relu_dx = false,
+                   int* relu_done = nullptr, const float* fold_slabs = nullptr, int fold_P = 0,
+                   float* fold_grp = nullptr, int* fold_done = nullptr, bool accum_slabs = false);
+int rk2_forward_impl(const void* x, void* xmid, void* y, uint8_t* mask1, uint8_t* mask2, const void* w,
+                     const float* bias, float h, int N, int H, int W, int C, int dtype, hipStream_t s);
+int rk2_backward_slabs(const void* dy, const void* x, const void* xmid, const uint8_t* mask1, const uint8_t* mask2,
+                       const void* w, float h, float gamma, int N, int H, int W, int C, int dtype, void* dx, void* g,
+                       bool need_w, float* slabs, float* dz_scratch, int* nsl, hipStream_t s,
+                       const float* fold_slabs = nullptr, int fold_P = 0, float* fold_grp = nullptr,
+                       int* fold_done = nullptr);
 int conv_backward_keep_slabs(const void* dy, const void* x, const uint8_t* mask, const void* w, float h, float gamma,
                              int N, int H, int W, int C, void* dx, void* ws, float* slabs, int* nsl, hipStream_t s);
-int relu_grad_bf16(void* d, const void* x, long n, hipStream_t s);
 // A stage whose L Euler blocks run in one launch: deep16 (bf16, 32 x 32 x 16) before the
 // image-resident kernels (stage_img_supported); the stack ABI and the multi-stage executor
 // run both through fused_stage_forward / fused_stage_backward.

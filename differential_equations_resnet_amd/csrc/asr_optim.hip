@@ -1,7 +1,7 @@
 // Device optimisers of the Keras training surface (asr_optimizer_update, include/asr.h): SGD with
 // momentum / Nesterov, Adam with AMSGrad, RMSprop, in the Keras 2.1.6-tf forms (the ones TF 1.12's
-// tf.keras.optimizers ships).  One launch per update whatever the optimiser, k_adam's grid-stride shape
-// (asr_api.hip), fp32 throughout, no host synchronisation.  The state is `slots` buffers of n floats,
+// tf.keras.optimizers ships), and the executors' plain Adam step (asr_adam_update, k_adam).  One launch
+// per update whatever the optimiser, k_adam's grid-stride shape, fp32 throughout, no host synchronisation.  The state is `slots` buffers of n floats,
 // back to back, owned and zero-initialised by the caller.
 //
 // Every element is read and written once per buffer it touches and nothing is reused, so the kernel
@@ -16,6 +16,19 @@
 #include "asr_common.h"
 
 namespace asr {
+
+__global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                       float* __restrict__ v, long n, float lr_t, float b1, float b2, float eps, float gscale) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float gi = g[i] * gscale;
+    const float mi = b1 * m[i] + (1.f - b1) * gi;
+    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    p[i] -= lr_t * mi / (sqrtf(vi) + eps);
+  }
+}
+
 namespace {
 
 struct OptParams {
@@ -75,6 +88,17 @@ bool kind_known(int kind) { return kind == ASR_OPT_SGD || kind == ASR_OPT_ADAM |
 using namespace asr;
 
 extern "C" {
+
+int asr_adam_update(float* params, const float* grads, float* m, float* v, long n, float lr, float beta1, float beta2,
+                    float eps, long step, float grad_scale, asr_stream_t stream) {
+  if (!params || !grads || !m || !v || n < 0 || step < 1) return fail(ASR_E_ARG, "asr_adam_update: bad arguments");
+  const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
+  const unsigned grid = (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, 4096));
+  hipLaunchKernelGGL(k_adam, dim3(grid), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, n, (float)lr_t,
+                     beta1, beta2, eps, grad_scale);
+  ASR_LAUNCH_CHECK("k_adam");
+  return ASR_OK;
+}
 
 int asr_optimizer_slots(int kind, int flags) {
   if (!kind_known(kind) || (flags & ~kind_flags(kind))) return -1;

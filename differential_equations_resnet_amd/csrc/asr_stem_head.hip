@@ -500,4 +500,26 @@ int head_param_grads(const float* gap, const float* dlogits, int N, int C, int K
   return ASR_OK;
 }
 
+// dz1 = dx1 * [x1 > 0] in place (bf16, 8 elements per thread): the stem's
+// relu' for networks whose first block's backward cannot fuse it (RK2)
+__global__ __launch_bounds__(256) void k_relu_grad_bf16(bf16* __restrict__ d, const bf16* __restrict__ x, long n8) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+    bf16x8 dv = ((const bf16x8*)d)[i];
+    const bf16x8 xv = ((const bf16x8*)x)[i];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dv[e] = (float)xv[e] > 0.f ? dv[e] : (bf16)0.f;
+    ((bf16x8*)d)[i] = dv;
+  }
+}
+
+// host: k_relu_grad_bf16 over n elements (n % 8 == 0), in place on d
+int relu_grad_bf16(void* d, const void* x, long n, hipStream_t s) {
+  if (n % 8) return fail(ASR_E_ARG, "relu_grad_bf16: n %% 8 != 0");
+  const long n8 = n / 8;
+  hipLaunchKernelGGL(k_relu_grad_bf16, dim3((unsigned)std::max<long>(1, std::min<long>((n8 + 255) / 256, 4096))),
+                     dim3(256), 0, s, (bf16*)d, (const bf16*)x, n8);
+  ASR_LAUNCH_CHECK("k_relu_grad_bf16");
+  return ASR_OK;
+}
+
 }  // namespace asr

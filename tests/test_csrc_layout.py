@@ -55,7 +55,7 @@ def internal_declarations():
         g = re.match(r"// ---- (\w+\.hip) -+$", line)
         if g:
             group = g.group(1)
-        m = re.match(r"(int|long|bool|size_t) (\w+)\(", line)
+        m = re.match(r"(int|long|bool|size_t|BwdWs) (\w+)\(", line)  # (BwdWs: a layout struct of asr_common.h)
         if m:
             assert group, f"{m.group(2)} is declared above the first file group"
             out.append((group, m.group(1), m.group(2)))

@@ -1,5 +1,5 @@
-"""GPU parity of the small kernels of asr_api.hip -- k_adam, k_segment_sq_norms,
-k_batch_metrics -- against numpy fp64, each called directly through runtime.
+"""GPU parity of the small kernels -- k_adam (asr_optim.hip), k_segment_sq_norms,
+k_batch_metrics (asr_api.hip) -- against numpy fp64, each called directly through runtime.
 
 Tolerances: Adam rtol 1e-6 + atol 1e-7 (tests/test_gpu_kernels.py) on the
 parameters and both moments; segment norms rtol 1e-5 (the bar of
