@@ -103,6 +103,15 @@ class OptimizerConfig(ct.Structure):
                 ("eps", ct.c_float), ("step", ct.c_long), ("grad_scale", ct.c_float)]
 
 
+ASR_REG_MAX_SEGMENTS = 256
+
+
+class RegSegment(ct.Structure):
+    """asr_reg_segment (include/asr.h)."""
+    _fields_ = [("offset", ct.c_long), ("count", ct.c_long), ("layer_stride", ct.c_long), ("layers", ct.c_int),
+                ("l2", ct.c_float), ("smooth", ct.c_float)]
+
+
 _P = ct.c_void_p
 _I = ct.c_int
 _L = ct.c_long
@@ -171,6 +180,9 @@ SIGNATURES = [
     ("asr_adam_update", _I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _L, _F, _P]),
     ("asr_optimizer_slots", _I, [_I, _I]),
     ("asr_optimizer_update", _I, [ct.POINTER(OptimizerConfig), _P, _P, _P, _L, _P]),
+    ("asr_regularize_check", _I, [_P, _I, _L]),
+    ("asr_regularize_workspace_bytes", _S, [_I, _L]),
+    ("asr_regularize", _I, [_P, _I, _P, _P, _F, _P, _P, _P, _S, _P]),
     ("asr_segment_sq_norms", _I, [_P, _P, _I, _P, _P]),
     ("asr_batch_metrics", _I, [_P, _P, _P, _I, _I, _P, _P]),
     ("asr_augment_batch", _I, [_P, _L, ct.POINTER(AugPlanConfig), _P, _I, _P, _P]),

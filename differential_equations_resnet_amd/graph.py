@@ -53,10 +53,14 @@ def _unique_name(base: str) -> str:
 
 
 class L2:
-    """tf.keras.regularizers.l2.  Kept for signature compatibility: the
-    reference's training driver ignores regularisation losses
-    (training/training.py:290-296, '#TODO regularization_losses'), and so does
-    this framework's."""
+    """tf.keras.regularizers.l2: the penalty l * sum(v ** 2) of the variable
+    it is attached to.  Model.losses lists the penalties, and compile / fit /
+    evaluate / train_on_batch / test_on_batch train and report loss +
+    sum(model.losses) as Keras does, the penalty and its gradient computed on
+    the device (asr_regularize over lowering's regularization_segments()).
+    Training adds them with regularization_losses=True; its default is the
+    reference's driver, which drops them (training/training.py:290-296,
+    '#TODO regularization_losses').  A coefficient of 0 is no regulariser."""
 
     def __init__(self, l=0.01):
         self.l2 = float(l)
@@ -498,6 +502,19 @@ class Model:
     @property
     def trainable_variables(self):
         return self.trainable_weights
+
+    @property
+    def losses(self):
+        """tf.keras Model.losses: the penalty l2 * sum(v ** 2) of every variable whose regulariser
+        has l2 > 0, in weight order, as floats computed on the host from the variables' current
+        values (the notebooks print the list; training adds the same terms on the device)."""
+        self._pull()
+        out = []
+        for w in self.weights:
+            r = w.regularizer
+            if isinstance(r, L2) and r.l2 > 0.0:
+                out.append(float(np.float64(np.float32(r.l2)) * np.sum(w.value.astype(np.float64) ** 2)))
+        return out
 
     def get_weights(self):
         self._pull()

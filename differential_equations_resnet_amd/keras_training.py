@@ -6,7 +6,13 @@ validation_data=(xv, yv))).
 
 A step is the executor's fused forward+backward, one optimiser launch
 (asr_optimizer_update) and one metrics launch (asr_batch_metrics); an evaluation
-step is the forward-only executor's forward and the metrics launch.  The arrays
+step is the forward-only executor's forward and the metrics launch.  A model
+with regularisers (l2_regularization, smoothness_regularization) also runs
+asr_regularize in each: between the backward and the update it adds the
+penalty's gradient to the executor's gradients and the penalty R to its loss,
+and in an evaluation step it adds R to the accumulated loss, so 'loss' and
+'val_loss' are Keras' loss + sum(model.losses).  A model without them makes no
+such call.  The arrays
 go to device memory once and a batch is an index gather there.  An epoch's last
 batch may be partial: it runs at its own size through a second executor (never
 padded: the loss is a mean over the batch).  asr_batch_metrics accumulates
@@ -161,6 +167,7 @@ class _Runner:
         labels = self._labels(labels, n)
         ex = self.native.executor(n, self.dtype, images.dtype == self.torch.uint8)
         loss, grads = ex.forward_backward(self.native.params, images, labels, want_probs=True)
+        self.native.regularize(grads, 1.0, loss)
         self.native.apply_optimizer(opt, grads)
         self.rt.batch_metrics(ex.probs, labels, loss, self.accum[0 if n == main else 1])
 
@@ -170,7 +177,9 @@ class _Runner:
         labels = self._labels(labels, n)
         ex = self.native.executor(n, self.dtype, images.dtype == self.torch.uint8, inference=True)
         probs = ex.forward(self.native.params, images)
-        self.rt.batch_metrics(probs, labels, None, self.accum[2 if n == main else 3])
+        row = self.accum[2 if n == main else 3]
+        self.rt.batch_metrics(probs, labels, None, row)
+        self.native.regularize(None, 1.0, row)  # row[0], the sum of the batches' losses, += R
 
     def rows(self):
         """One device read: the four accumulator rows [sum of batch-mean losses, correct, samples, batches]."""

@@ -52,7 +52,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from .graph import (Activation, Add, Conv2D, Dense, GlobalAveragePooling2D, InputLayer, Lambda, Model,
+from .graph import (L2, Activation, Add, Conv2D, Dense, GlobalAveragePooling2D, InputLayer, Lambda, Model,
                     SymbolicTensor)
 from .layers._antisymmetric import AntisymmetricConvBase
 
@@ -79,6 +79,7 @@ class NetPlan:
     fc: Dense = None
     kernel_size: int = 3        # the blocks' (asr_net_config.kernel_size)
     conv1_kernel_size: int = 3  # conv1's (asr_net_config.conv1_kernel_size)
+    smoothness_regularization: float = 0.0  # the blocks' alpha (single_layer_identity_block)
 
     def weight_vars(self):
         """Variables in the executor's flat order (Keras get_weights order)."""
@@ -91,6 +92,11 @@ class NetPlan:
     def block_theta_sizes(self):
         """Per block: number of theta (kernel) floats, excluding the bias."""
         return [sum(v.value.size for v in conv.weights) - self.C for conv in self.blocks]
+
+    def regularization_segments(self):
+        """The asr_reg_segment rows (offset, count, layer_stride, layers, l2, smooth) of this
+        model's regularisers over weight_vars(); [] when every coefficient is zero."""
+        return _regularization_segments(self, [(None, self.blocks)])
 
 
 @dataclass
@@ -113,6 +119,7 @@ class StagesPlan:
     integrator: str = "euler"
     conv1: Conv2D = None
     fc: Dense = None
+    smoothness_regularization: float = 0.0  # the blocks' alpha (single_layer_identity_block)
 
     @property
     def blocks(self):
@@ -150,6 +157,85 @@ class StagesPlan:
                 out += conv.weights
         out += [self.fc.kernel, self.fc.bias]
         return out
+
+    def regularization_segments(self):
+        """As NetPlan.regularization_segments; the smoothness penalty joins the identity blocks of
+        one stage only, never two stages across a transition."""
+        return _regularization_segments(self, list(zip(self.transitions, self.stage_blocks)))
+
+
+def _l2_coefficient(v) -> float:
+    """The l2 coefficient of a variable's regulariser (0.0 without one), as the float32 the ABI carries."""
+    r = v.regularizer
+    if r is None:
+        return 0.0
+    if v.name.endswith("/bias"):
+        raise _lib.AsrUnsupported(f"{v.name}: a bias_regularizer is not supported (kernel_regularizer=l2(...) is)")
+    if not isinstance(r, L2):
+        raise _lib.AsrUnsupported(f"{v.name}: regulariser {r!r} is not supported (graph.l2 is)")
+    if not (r.l2 >= 0.0 and np.isfinite(r.l2)):
+        raise ValueError(f"{v.name}: l2 coefficient {r.l2!r} must be finite and >= 0")
+    return float(np.float32(r.l2))
+
+
+def _regularization_segments(plan, stages):
+    """stages: [(transition convs or None, the stage's identity-block convs)] in weight_vars() order.
+
+    A plain variable with l2 > 0 is one segment of one layer.  The identity blocks of a stage lie
+    back to back, each [theta variables..., bias], so the thetas of consecutive blocks with equal
+    coefficients are ONE strided segment (layers = blocks, layer_stride = n_theta + C): a deep net
+    stays far below the table's 256 rows.  With smoothness_regularization = alpha > 0 that segment
+    carries smooth = alpha / (2h), and a second one at the same stride covers the biases."""
+    pos, off = {}, 0
+    for v in plan.weight_vars():
+        pos[id(v)] = off
+        off += v.value.size
+    coef = {id(v): _l2_coefficient(v) for v in plan.weight_vars()}
+    alpha = float(plan.smoothness_regularization)
+    smooth = float(np.float32(alpha / (2.0 * plan.h))) if alpha > 0.0 else 0.0
+    segs = []
+
+    def plain(v):
+        if coef[id(v)] > 0.0:
+            segs.append((pos[id(v)], v.value.size, v.value.size, 1, coef[id(v)], 0.0))
+
+    def runs(conv):
+        """A block's theta variables as (offset in the block, count, l2), neighbours with one l2 merged."""
+        out, rel = [], 0
+        for v in conv.weights[:-1]:
+            if out and out[-1][2] == coef[id(v)]:
+                out[-1] = (out[-1][0], out[-1][1] + v.value.size, out[-1][2])
+            else:
+                out.append((rel, v.value.size, coef[id(v)]))
+            rel += v.value.size
+        return out, rel, conv.weights[-1].value.size
+
+    plain(plan.conv1.kernel)
+    for tr, blocks in stages:
+        if tr is not None:
+            plain(tr[0].kernel)
+            plain(tr[1].kernel)
+        groups = []  # consecutive blocks of one layout: [first block, its runs, n_theta, C, count]
+        for conv in blocks:
+            r, nt, C = runs(conv)
+            if groups and groups[-1][1:4] == [r, nt, C]:
+                groups[-1][4] += 1
+            else:
+                groups.append([conv, r, nt, C, 1])
+        if smooth > 0.0 and len(groups) > 1:
+            raise _unsupported(groups[1][0], "smoothness_regularization needs the identity blocks of a stage to "
+                                             "share their l2 coefficients")
+        for conv, r, nt, C, n in groups:
+            base, sm = pos[id(conv.weights[0])], (smooth if n > 1 else 0.0)
+            for rel, count, c in r:
+                if c > 0.0 or sm > 0.0:
+                    segs.append((base + rel, count, nt + C, n, c, sm))
+            if sm > 0.0:
+                segs.append((base + nt, C, nt + C, n, 0.0, sm))
+    plain(plan.fc.kernel)
+    if len(segs) > _lib.ASR_REG_MAX_SEGMENTS:
+        raise _lib.AsrUnsupported(f"{len(segs)} regulariser segments (at most {_lib.ASR_REG_MAX_SEGMENTS})")
+    return segs
 
 
 def _transition(t: SymbolicTensor):
@@ -320,6 +406,9 @@ def analyze(model: Model) -> NetPlan:
               float(getattr(b, "gamma", 0.0))) for b in blocks}
     if len(kinds) != 1 or len(set(hs)) != 1 or len(set(integ)) != 1:
         raise _lib.AsrUnsupported("all identity blocks must share conv type, gamma, h and integrator")
+    alphas = sorted({float(getattr(b, "smoothness_regularization", 0.0)) for b in blocks})
+    if len(alphas) != 1:
+        raise _lib.AsrUnsupported(f"all identity blocks must share one smoothness_regularization (got {alphas})")
     kb = _block_kernel_size(first)
     for b in blocks:
         if _block_kernel_size(b) != kb:
@@ -335,10 +424,11 @@ def analyze(model: Model) -> NetPlan:
                 raise _unsupported(layer, f"multi-stage nets run 3x3 convs only (conv1, blocks and transitions; "
                                           f"kernel_size {k})")
         return _stages_plan(segs, int(H), int(W), int(Cin), int(C), fc, float(hs[0]), gamma, mean, std, kind, anti,
-                            integ[0], conv1)
+                            integ[0], conv1, alphas[0])
     plan = NetPlan(H=int(H), W=int(W), Cin=int(Cin), C=int(C), L=len(blocks), num_classes=fc.units, h=float(hs[0]),
                    gamma=gamma, subtract_mean=mean, divide_by_stddev=std, param_kind=kind, antisymmetric=anti,
-                   integrator=integ[0], conv1=conv1, blocks=blocks, fc=fc, kernel_size=kb, conv1_kernel_size=k1)
+                   integrator=integ[0], conv1=conv1, blocks=blocks, fc=fc, kernel_size=kb, conv1_kernel_size=k1,
+                   smoothness_regularization=alphas[0])
     if kb != 3 and integ[0] != "euler":
         raise _unsupported(first, f"RK2 blocks need kernel size 3 (kernel_size {kb})")
     for b in blocks:
@@ -347,7 +437,7 @@ def analyze(model: Model) -> NetPlan:
     return plan
 
 
-def _stages_plan(segs, H, W, Cin, C0, fc, h, gamma, mean, std, kind, anti, integrator, conv1) -> StagesPlan:
+def _stages_plan(segs, H, W, Cin, C0, fc, h, gamma, mean, std, kind, anti, integrator, conv1, alpha=0.0) -> StagesPlan:
     if integrator != "euler":
         raise _lib.AsrUnsupported("multi-stage nets run Euler identity blocks (integrator='rk2' is single-stage)")
     if len(segs) > _lib.ASR_STAGES_MAX:
@@ -369,7 +459,8 @@ def _stages_plan(segs, H, W, Cin, C0, fc, h, gamma, mean, std, kind, anti, integ
         Cp = C
     return StagesPlan(H=H, W=W, Cin=Cin, num_classes=fc.units, h=h, gamma=gamma, subtract_mean=mean,
                       divide_by_stddev=std, param_kind=kind, antisymmetric=anti, stages=stages,
-                      transitions=transitions, stage_blocks=stage_blocks, integrator=integrator, conv1=conv1, fc=fc)
+                      transitions=transitions, stage_blocks=stage_blocks, integrator=integrator, conv1=conv1, fc=fc,
+                      smoothness_regularization=alpha)
 
 
 class NativeModel:
@@ -403,6 +494,7 @@ class NativeModel:
         self.step = 0
         self.opt = None        # the optimizers.Optimizer whose state opt_state holds
         self.opt_state = None  # [slots * n_params] float32, apply_optimizer
+        self._reg = None       # runtime.RegTable of plan.regularization_segments(), regularizer()
         self._host_stale = False
         self.push_weights()
 
@@ -493,6 +585,21 @@ class NativeModel:
         if x.dtype not in (torch.uint8, torch.float32):
             x = x.float()
         return x.to(self.device, non_blocking=True).contiguous()
+
+    def regularizer(self):
+        """The model's regulariser segments on the device (runtime.RegTable; checked, uploaded and
+        given their workspace on first use), or None when the model has none: then no call is made
+        and a step is the step of a model built without regularisers."""
+        if self._reg is None:
+            self._reg = self._rt.RegTable(self.plan.regularization_segments(), self.n_params, self.device)
+        return self._reg if self._reg.n else None
+
+    def regularize(self, grads=None, grad_scale=1.0, loss=None):
+        """grads += dR / grad_scale and loss[0] += R for the model's penalty R (asr_regularize);
+        nothing without regularisers."""
+        reg = self.regularizer()
+        if reg is not None:
+            self._rt.regularize(reg, self.params, grads, grad_scale, loss)
 
     def apply_adam(self, grads, lr, beta1=0.9, beta2=0.999, epsilon=1e-7, grad_scale=1.0):
         torch = self._torch

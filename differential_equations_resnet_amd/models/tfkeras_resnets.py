@@ -53,7 +53,8 @@ def _conv(x, filters, kernel_size, name, strides=(1, 1), padding="same", kernel_
 
 
 def single_layer_identity_block(input_tensor, kernel_size, antisymmetric, use_batch_norm, stage, block, h=1.0,
-                                gamma=0.0, kernel_regularizer=None, bias_regularizer=None, integrator="euler"):
+                                gamma=0.0, kernel_regularizer=None, bias_regularizer=None, integrator="euler",
+                                smoothness_regularization=0.0):
     """One Euler step x + h*relu(conv(x)) (tfkeras_resnets.py:28-94): the
     conv is Conv2DAntisymmetric3By3 when `antisymmetric`, else a regular
     'same' Conv2D with C filters; optional BN after it; the h-scaling Lambda
@@ -63,9 +64,19 @@ def single_layer_identity_block(input_tensor, kernel_size, antisymmetric, use_ba
     builds the explicit midpoint step with the SAME conv layer (shared
     weights) applied twice:
         xm = x + (h/2)*relu(conv(x)),   out = x + h*relu(conv(xm))
-    with the half-step scaling Lambda named scale{stage}_{block}_half."""
+    with the half-step scaling Lambda named scale{stage}_{block}_half.
+
+    smoothness_regularization=alpha > 0 (extension: the regulariser Haber &
+    Ruthotto pair with this architecture, R = alpha / (2h) * sum_j ||K_j -
+    K_{j-1}||^2) marks the block's conv, kernel and bias, to be kept close to
+    those of the identity blocks next to it in its stage; the penalty is
+    formed where the model is lowered (lowering.regularization_segments), so
+    it is trained by compile / fit like an l2 regulariser and, as a sum over
+    pairs of layers, is not part of Model.losses."""
     if integrator not in ("euler", "rk2"):
         raise ValueError(f"integrator must be 'euler' or 'rk2', got {integrator!r}")
+    if not (float(smoothness_regularization) >= 0.0 and np.isfinite(smoothness_regularization)):
+        raise ValueError(f"smoothness_regularization must be finite and >= 0, got {smoothness_regularization!r}")
     conv_name, bn_name = _names(stage, block)
     if antisymmetric:
         conv = _antisym_conv_layer(gamma, (1, 1), kernel_regularizer, conv_name + "2")
@@ -73,6 +84,7 @@ def single_layer_identity_block(input_tensor, kernel_size, antisymmetric, use_ba
         conv = Conv2D(filters=int(input_tensor.shape[-1]), kernel_size=kernel_size, strides=(1, 1), padding="same",
                       kernel_initializer="he_normal", kernel_regularizer=kernel_regularizer,
                       bias_regularizer=bias_regularizer, name=conv_name + "2")
+    conv.smoothness_regularization = float(smoothness_regularization)
     if integrator == "rk2":
         if use_batch_norm:
             raise ValueError("integrator='rk2' does not support use_batch_norm")
@@ -190,10 +202,11 @@ def get_single_block_resnet_build_function(kernel_type="antisymmetric", kernel_s
                                            fc_activation="softmax", num_classes=None, use_batch_norm=False,
                                            use_max_pooling=[False, False, False, False], l2_regularization=0.0,
                                            subtract_mean=None, divide_by_stddev=None, verbose=False,
-                                           integrator="euler"):
+                                           integrator="euler", smoothness_regularization=0.0):
     """Returns build(input_tensor) -> Model for the single-conv-per-block
     ResNet (tfkeras_resnets.py:511-604).  `integrator` (extension, default
-    the reference's forward Euler) is passed to every identity block."""
+    the reference's forward Euler) and `smoothness_regularization`
+    (extension, default none) are passed to every identity block."""
     if include_top and num_classes is None:
         raise ValueError("You must pass a positive integer for `num_classes` if `include_top` is `True`.")
     antisymmetric = kernel_type == "antisymmetric"
@@ -216,7 +229,8 @@ def get_single_block_resnet_build_function(kernel_type="antisymmetric", kernel_s
                 print(f"Building identity block {stage}-{b + 1}")
             return single_layer_identity_block(x, kernel_size, antisymmetric, use_batch_norm, stage=stage, block=b,
                                                h=h, gamma=gamma, kernel_regularizer=l2(l2_regularization),
-                                               integrator=integrator)
+                                               integrator=integrator,
+                                               smoothness_regularization=smoothness_regularization)
 
         for s in range(num_stages - 1):
             stage = s + 2
@@ -248,14 +262,15 @@ def build_single_block_resnet(image_shape, kernel_type="antisymmetric", kernel_s
                               strides=[(2, 2), (2, 2), (2, 2), (2, 2)], include_top=True, fc_activation="softmax",
                               num_classes=None, use_batch_norm=False, use_max_pooling=[False, False, False, False],
                               l2_regularization=0.0, subtract_mean=None, divide_by_stddev=None, verbose=False,
-                              integrator="euler"):
+                              integrator="euler", smoothness_regularization=0.0):
     """tfkeras_resnets.py:427-509: build function applied to Input(image_shape)."""
     fn = get_single_block_resnet_build_function(
         kernel_type=kernel_type, kernel_size=kernel_size, h=h, gamma=gamma, num_stages=num_stages,
         blocks_per_stage=blocks_per_stage, filters_per_block=filters_per_block, strides=strides,
         include_top=include_top, fc_activation=fc_activation, num_classes=num_classes, use_batch_norm=use_batch_norm,
         use_max_pooling=use_max_pooling, l2_regularization=l2_regularization, subtract_mean=subtract_mean,
-        divide_by_stddev=divide_by_stddev, verbose=verbose, integrator=integrator)
+        divide_by_stddev=divide_by_stddev, verbose=verbose, integrator=integrator,
+        smoothness_regularization=smoothness_regularization)
     return fn(Input(shape=image_shape))
 
 

@@ -22,7 +22,8 @@ __all__ = [
     "require_gpu", "dtype_code", "torch_dtype", "ParamMap", "param_map", "theta_count", "theta_to_w",
     "conv_forward", "block_stack_forward", "block_stack_backward", "conv_backward", "rk2_forward", "rk2_backward",
     "integrator_code", "NetExecutor", "adam_update", "stack_status", "transition_forward", "transition_backward",
-    "StagesExecutor", "augment_batch", "optimizer_slots", "optimizer_update",
+    "StagesExecutor", "augment_batch", "optimizer_slots", "optimizer_update", "reg_segments", "regularize_check",
+    "RegTable", "regularize",
 ]
 
 
@@ -436,6 +437,59 @@ def optimizer_update(cfg, params, grads, state):
         if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError(f"optimizer_update: {name} must be a contiguous float32 device tensor")
     _lib.call("asr_optimizer_update", ct.byref(cfg), _p(params), _p(grads), _p(state), n, _stream())
+
+
+def reg_segments(segments) -> "ct.Array":
+    """The host asr_reg_segment table of `segments`: _lib.RegSegment objects or (offset, count,
+    layer_stride, layers, l2, smooth) tuples."""
+    rows = [s if isinstance(s, _lib.RegSegment) else _lib.RegSegment(*s) for s in segments]
+    return (_lib.RegSegment * max(len(rows), 1))(*rows)
+
+
+def regularize_check(segments, n_params: int) -> None:
+    """asr_regularize_check on a host table (no device use): ValueError naming the malformed segment."""
+    segments = list(segments)
+    _lib.call("asr_regularize_check", ct.cast(reg_segments(segments), ct.c_void_p), len(segments), int(n_params))
+
+
+class RegTable:
+    """A checked segment table on the device with the workspace of its calls: built (and uploaded)
+    once, then every regularize() with it is launches only."""
+
+    def __init__(self, segments, n_params: int, device=None):
+        segments = list(segments)
+        regularize_check(segments, n_params)
+        self.n = len(segments)
+        self.n_params = int(n_params)
+        self.table = self.ws = None
+        self.ws_bytes = 0
+        if self.n == 0:  # nothing to upload: regularize() launches nothing
+            return
+        self.device = torch.device(device) if device is not None else require_gpu()
+        host = reg_segments(segments)
+        raw = np.frombuffer(host, dtype=np.uint8, count=max(self.n, 1) * ct.sizeof(_lib.RegSegment)).copy()
+        self.table = torch.from_numpy(raw).to(self.device)
+        self.ws_bytes = int(_lib.load().asr_regularize_workspace_bytes(self.n, self.n_params))
+        self.ws = torch.empty(max(self.ws_bytes, 8), dtype=torch.uint8, device=self.device)
+
+
+def regularize(table: RegTable, params, grads=None, grad_scale: float = 1.0, loss=None, penalty=None):
+    """R = the l2 and smoothness penalties of the table's segments of the flat float32 `params`
+    (asr_regularize): grads += dR / grad_scale (grads None: forward only), loss[0] += R and
+    penalty[0] = R for the device float32 tensors given.  No allocation, no host synchronisation; an
+    empty table launches nothing."""
+    if table.n == 0:
+        return
+    for name, t in (("params", params), ("grads", grads)):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()
+                              or t.numel() != table.n_params):
+            raise ValueError(f"regularize: {name} must be a contiguous float32 device tensor of {table.n_params} "
+                             "elements")
+    for name, t in (("loss", loss), ("penalty", penalty)):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.numel() < 1):
+            raise ValueError(f"regularize: {name} must be a float32 device tensor")
+    _lib.call("asr_regularize", _p(table.table), table.n, _p(params), _p(grads), float(grad_scale), _p(loss),
+              _p(penalty), _p(table.ws), table.ws_bytes, _stream())
 
 
 def augment_batch(features, plan, items, out=None):

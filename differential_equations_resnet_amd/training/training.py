@@ -4,7 +4,11 @@ instead of a TF1 Session.
 
 Semantics kept from the reference:
   * loss = mean Keras categorical cross-entropy on the softmax outputs
-    (:290-296), regularisation losses ignored (the reference's TODO);
+    (:290-296), regularisation losses ignored (the reference's TODO) unless
+    regularization_losses=True (extension): then every step adds the model's
+    l2 / smoothness penalty R and its gradient on the device (asr_regularize,
+    after the all-reduce) and mean_loss, in training and evaluation, is the
+    cross-entropy + R, as Keras' fit reports it;
   * tf.train.AdamOptimizer with the epsilon-hat update (:297-300), or one of
     optimizers.SGD / Adam / RMSprop (the notebooks' tf.keras.optimizers
     alternative), applied by asr_optimizer_update;
@@ -72,7 +76,8 @@ class Training:
                  train_labels_placeholder=None, val_features_placeholder=None, val_labels_placeholder=None,
                  train_features=None, train_labels=None, val_features=None, val_labels=None, global_step=0,
                  num_layers=None, record_summaries=True, summaries=["mean_gradient_norms"], summaries_dir=None,
-                 summaries_name=None, csv_logger_dir=None, csv_logger_name=None, dtype=None):
+                 summaries_name=None, csv_logger_dir=None, csv_logger_name=None, dtype=None,
+                 regularization_losses=False):
         import torch
         if train_dataset is None or not hasattr(train_dataset, "__iter__"):
             raise ValueError("train_dataset must be an ArrayDataset (dataset_utils) or another iterable of "
@@ -98,6 +103,7 @@ class Training:
         self.summaries_name = summaries_name
         self.csv_logger_dir = csv_logger_dir
         self.csv_logger_name = csv_logger_name
+        self.regularization_losses = bool(regularization_losses)
         self.variables_updated = False
         self.eval_dataset = None
         self.training_loss = None
@@ -248,6 +254,8 @@ class Training:
         labels = self._targets(labels)
         loss, grads, probs = self.native.forward_backward(images, labels, want_probs=True)
         distributed.allreduce_grads(grads)
+        if self.regularization_losses:  # the update multiplies by 1/world: it sees dR once
+            self.native.regularize(grads, 1.0 / self.world, loss)
         norms = self._gradient_mean_norms(grads) if with_norms else None
         opt = self.optimizer
         if isinstance(opt, AdamOptimizer):
@@ -356,6 +364,8 @@ class Training:
                 ex_u8 = self.native.executor(images.dtype == self._torch.uint8, inference=True)
             probs = ex_u8.forward(self.native.params, images)
             runtime.batch_metrics(probs, labels, None, self._accum)
+            if self.regularization_losses:
+                self.native.regularize(None, 1.0, self._accum)  # accum[0], the sum of the batches' losses, += R
         self.metric_values = self._metric_values()
 
     def evaluate(self, eval_dataset="val", num_batches=1, dataset="val"):

@@ -636,6 +636,67 @@ int asr_optimizer_slots(int kind, int flags);
 int asr_optimizer_update(const asr_optimizer_config* cfg, float* params, const float* grads,
                          float* state, long n, asr_stream_t stream);
 
+/* Weight regularisers of the same surface (additional exports of ABI 12):
+ * Keras' l2 (tf.keras.regularizers.l2, which Model.fit adds to the loss it
+ * trains and reports) and the smoothness-in-depth penalty of Haber & Ruthotto,
+ * "Stable architectures for deep neural networks", R = 1/(2h) sum_j ||K_j -
+ * K_{j-1}||^2, over a table of segments of the flat parameter buffer.  A
+ * segment is `layers` runs of `count` floats, layer_stride floats apart (one
+ * run for a plain variable; a stack of identity blocks has its thetas, and
+ * its biases, at the stride n_theta + C).  With p_l[j] float j of layer l:
+ *   R     = sum over segments of  l2 * sum p^2
+ *                               + smooth * sum_{l>=1} sum_j (p_l[j] - p_{l-1}[j])^2
+ *   dR/dp_l[j] = 2 l2 p_l[j] + 2 smooth ((p_l - p_{l-1})[j] [l > 0]
+ *                                        + (p_l - p_{l+1})[j] [l < layers - 1])
+ * asr_regularize, with grads:   grads[i] += dR/dp[i] / grad_scale for every
+ *   covered float i (grad_scale is what the optimiser launch will multiply g
+ *   by, 1/world or 1: the update sees dR once, so the call goes after the
+ *   all-reduce); grads == NULL is the forward-only form of evaluation;
+ * with loss_inout:  *loss_inout += R;   with penalty_out:  *penalty_out = R.
+ * Floats no segment covers (the biases between two layers' thetas when
+ * layer_stride > count) are neither read for R nor written in grads, and
+ * nothing outside params / grads / the workspace / the two scalars is touched.
+ *
+ * Contract, as for every call of this header: no allocation, no host
+ * synchronisation, every launch on `stream` (capturable into a HIP graph),
+ * prior workspace contents irrelevant.  Two launches at most (one without
+ * loss_inout and penalty_out) whatever n_segments is; none for n_segments ==
+ * 0, which is ASR_OK.  R and dR are formed in fp64 from the fp32 parameters;
+ * the workgroups' partial sums of R are stored in the workspace and summed
+ * in a fixed order (no floating-point atomics), so R and grads are bitwise
+ * reproducible for equal arguments (the workspace size included: one
+ * workgroup runs per 8 bytes of it, at most 1024).  Accesses are 16 bytes
+ * wide where offset, count and layer_stride are multiples of 4 floats (count
+ * free for layers == 1) and params / grads are 16-byte aligned.
+ *
+ * `segments` of asr_regularize is a DEVICE copy of the table, which the call
+ * cannot inspect: the caller checks the host table once with
+ * asr_regularize_check before uploading it.  That returns ASR_E_ARG (the
+ * segment named in asr_last_error) for n_segments outside 0..256; count < 1,
+ * layers < 1 or layer_stride < count; a segment that ends beyond n_params; a
+ * negative or non-finite coefficient; two segments whose covered floats
+ * overlap (segments may interleave: thetas and biases at one stride).
+ * asr_regularize itself returns ASR_E_ARG for n_segments outside 0..256, a
+ * null segments / params or, with grads, a grad_scale that is not finite and
+ * positive, and ASR_E_WORKSPACE for a workspace below 8 bytes or not 8-byte
+ * aligned (any size from 8 bytes on computes the same sums, slower). */
+typedef struct asr_reg_segment {
+  long offset;       /* first float of layer 0 in the flat parameter buffer   */
+  long count;        /* floats per layer                                      */
+  long layer_stride; /* layer l starts at offset + l*layer_stride (>= count)  */
+  int layers;        /* >= 1; 1 for a plain variable                          */
+  float l2;          /* Keras l2(l):  R += l2 * sum p^2                       */
+  float smooth;      /* R += smooth * sum_{l>=1} sum_j (p_l[j] - p_{l-1}[j])^2 */
+} asr_reg_segment;
+#define ASR_REG_MAX_SEGMENTS 256
+/* Host only. */
+int asr_regularize_check(const asr_reg_segment* host_segments, int n_segments, long n_params);
+/* Host only: 0 for n_segments outside 1..256 or n_params < 0. */
+size_t asr_regularize_workspace_bytes(int n_segments, long n_params);
+int asr_regularize(const asr_reg_segment* segments, int n_segments, const float* params, float* grads,
+                   float grad_scale, float* loss_inout, float* penalty_out, void* ws, size_t ws_bytes,
+                   asr_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Training-loop metrics, accumulated on the device (no per-step host sync).
  * ---------------------------------------------------------------------- */
