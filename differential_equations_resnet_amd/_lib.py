@@ -29,7 +29,7 @@ ASR_BF16 = 1
 ASR_PARAM_3BY3 = 0
 ASR_PARAM_GENERAL = 1
 ASR_PARAM_REGULAR = 2
-ABI_VERSION = 12
+ABI_VERSION = 13
 ASR_MODE_EULER = 0
 ASR_MODE_CONV = 1
 ASR_INTEGRATOR_EULER = 0
@@ -143,6 +143,7 @@ SIGNATURES = [
                                       _P]),
     ("asr_wpack_elems", _L, [_I]),
     ("asr_theta_to_w", _I, [_P, _L, _I, _I, _P, _F, _P, _L, _I, _P]),
+    ("asr_theta_to_w_mirror", _I, [_P, _L, _I, _I, _P, _P, _L, _I, _P]),
     ("asr_conv_forward", _I, [_I, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P]),
     ("asr_mask_bytes", _L, [_I, _I, _I, _I]),
     ("asr_block_stack_forward", _I, [_P, _P, _L, _P, _L, _P, _L, _P, _L, _F, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -70,6 +70,10 @@ struct PackJob {
   // coalesced and no pairing check; nullptr: the entries gathered through w_src and checked
   const int32_t* theta_dst;
   long n_theta;
+  // 1: w_src is asr_param_map_transpose's map of a forward job's map; the pack is then -flip(W)^T of
+  // that job's pack entry for entry (the forward's rounding decisions, asr_theta.hip).  The caller
+  // says so: the kernel does not guess it from the map
+  int mirror;
 };
 
 // Slab layout of the pair-local C=64 stacked backward (k_bwd3_stack<..., PAIR>,

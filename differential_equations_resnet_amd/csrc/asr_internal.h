@@ -53,7 +53,7 @@ constexpr int kMaxPackJobs = 16;
 int theta_to_w_bf16_jobs(const PackJob* jobs, int njobs, hipStream_t s);
 int theta_to_w_bf16(const float* theta, long theta_stride, int L, int C, const int32_t* w_src, float gamma, void* w,
                     long w_stride, bool balance, hipStream_t s, const int32_t* theta_dst = nullptr,
-                    long n_theta = 0);
+                    long n_theta = 0, bool mirror = false);
 int reduce_and_project(const float* slabs, int P, long E, int Cb, const int32_t* theta_dst, long n_theta,
                        float* dtheta, float* dbias, float* dw_out, float* ws, hipStream_t s);
 size_t reduce_ws_bytes(int P, long ES);

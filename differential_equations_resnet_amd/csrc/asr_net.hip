@@ -413,8 +413,9 @@ struct NetFwd {
   const float* bias(int l) const { return params + L.off_blk + (long)l * L.blk_stride + L.ntheta; }
 };
 
-// 1. W for all L blocks, one launch; training with an operator that is not antisymmetric: W_bwd = -flip(W)^T
-// as well, from the transposed map and without the gamma term
+// 1. W for all L blocks, one launch; training with an operator that is not antisymmetric: W_bwd as well,
+// from the transposed map and without the gamma term.  It is -flip(W)^T of the W just packed, entry for
+// entry: round to nearest gives that by itself, the balanced pack as a mirror job (PackJob::mirror)
 static int net_materialise_w(const NetFwd& f) {
   const asr_net_config* c = f.c;
   const NetLayout& L = f.L;
@@ -436,7 +437,8 @@ static int net_materialise_w(const NetFwd& f) {
         const bool paired = !bwd && c->param_kind != ASR_PARAM_REGULAR;
         ASR_TRY(theta_to_w_bf16(th, L.blk_stride, c->L, c->C, src, gamma, w, L.wstride,
                                 L.plan.w_pack == WPack::kBf16Bal, f.s,
-                                paired ? (const int32_t*)(f.ws + L.theta_dst) : nullptr, bwd ? 0 : L.ntheta));
+                                paired ? (const int32_t*)(f.ws + L.theta_dst) : nullptr, bwd ? 0 : L.ntheta,
+                                bwd != 0));
         break;
       }
       case WPack::kF32:

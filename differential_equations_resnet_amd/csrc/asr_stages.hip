@@ -1181,17 +1181,17 @@ int stages_forward_impl(const asr_stages_config* c, const SLayout& L, const floa
     if (pack)
       jobs[nj++] = {params + g.off_blk, g.blk_stride, g.L, g.C, (const int32_t*)(b + g.w_src), c->gamma, b + g.wbuf,
                     g.wstride, c->param_kind != ASR_PARAM_REGULAR ? (const int32_t*)(b + g.theta_dst) : nullptr,
-                    g.ntheta};
+                    g.ntheta, 0};
     else
       ASR_TRY(asr_theta_to_w(params + g.off_blk, g.blk_stride, g.L, g.C, (const int32_t*)(b + g.w_src), c->gamma,
                              b + g.wbuf, g.wstride, wdt, s));
-    if (training && L.sep_bwd) {
+    if (training && L.sep_bwd) {  // W_bwd = -flip(W)^T of the pack above, entry for entry: a mirror job
       if (pack)
         jobs[nj++] = {params + g.off_blk, g.blk_stride, g.L, g.C, (const int32_t*)(b + g.w_src_bwd), 0.f,
-                      b + g.wbuf_bwd, g.wstride, nullptr, 0};
+                      b + g.wbuf_bwd, g.wstride, nullptr, 0, 1};
       else
-        ASR_TRY(asr_theta_to_w(params + g.off_blk, g.blk_stride, g.L, g.C, (const int32_t*)(b + g.w_src_bwd), 0.f,
-                               b + g.wbuf_bwd, g.wstride, wdt, s));
+        ASR_TRY(asr_theta_to_w_mirror(params + g.off_blk, g.blk_stride, g.L, g.C, (const int32_t*)(b + g.w_src_bwd),
+                                      b + g.wbuf_bwd, g.wstride, wdt, s));
     }
   }
   if (nj) ASR_TRY(theta_to_w_bf16_jobs(jobs, nj, s));

@@ -285,8 +285,9 @@ __global__ void k_theta_to_w_pack(const float* __restrict__ theta, long theta_st
 // kappa >= taps*C; KS = ceil(taps*C / 32)), the bf16 W of asr_conv_kxk.hip.  Round to nearest
 // even: it commutes with negation and with the flip / transpose permutation, so the pack of an
 // antisymmetric map stays exactly antisymmetric off the diagonal and the pack of
-// asr_param_map_transpose_k's map is bit for bit -flip(W)^T of the forward pack.  (The balanced
-// rounding below removes an error that only a deep stack sees; nothing stacks k != 3 layers.)
+// asr_param_map_transpose_k's map is bit for bit -flip(W)^T of the forward pack.  (That holds for
+// round to nearest only: the balanced rounding below needs PackJob::mirror for it.  It removes an
+// error that only a deep stack sees; nothing stacks k != 3 layers.)
 __global__ void k_theta_to_w_pack_k(const float* __restrict__ theta, long theta_stride, int C, int taps,
                                     const int32_t* __restrict__ w_src, float gamma, bf16* __restrict__ w,
                                     long w_stride) {
@@ -333,6 +334,14 @@ __global__ void k_theta_to_w_pack_k(const float* __restrict__ theta, long theta_
 // diagonal entries rounded to nearest (taps 0..8; the centre gamma, and the
 // mirrored diagonal pairs of the non-antisymmetric general kind);
 // tests/helpers.py w_bf16_balanced restates it bit-exactly.
+// The mirror W_bwd = -flip(W)^T of a map that is not antisymmetric (asr_param_map_transpose:
+// the same off-diagonal entries, the diagonal negated and its taps reversed) packed as a plain
+// job would start every sum from the opposite sign and decide its pairs differently: the
+// backward would read another W than the forward.  PackJob::mirror says that the job's map is
+// such a transpose; its sums then start from the forward's diagonal errors, term t from the
+// negated error of the job's own entry at tap 8 - t (round to nearest even commutes with
+// negation, so that is the forward's term t exactly), every pair takes the forward's
+// neighbour, and the pack is -flip(W)^T of the forward pack, entry for entry.
 __device__ __forceinline__ unsigned wpack_pos(int KS, int o, int kappa) {
   const int r = kappa & 31;
   return (unsigned)((((o >> 4) * KS + (kappa >> 5)) * 64 + (o & 15) + 16 * (r >> 3)) * 8 + (r & 7));
@@ -369,7 +378,7 @@ template <int C>
 __device__ __forceinline__ void pack_bal_layer(const float* __restrict__ theta, long theta_stride,
                                                const int32_t* __restrict__ w_src, float gamma, bf16* __restrict__ w,
                                                long w_stride, const int32_t* __restrict__ theta_dst, long n_theta,
-                                               int l, unsigned char* lds) {
+                                               bool mirror, int l, unsigned char* lds) {
   constexpr int KS = (9 * C + 31) / 32, LC = C == 16 ? 4 : C == 32 ? 5 : 6, NP = C / 2, NR = C - 1;
   constexpr int NQ = NR * NP * 9, NIT = (NQ + kBalThreads - 1) / kBalThreads, NB = NIT < 9 ? NIT : 9;
   constexpr int R = C == 64 ? 4 : 2, NS = (NR + R - 1) / R, SQ = R * NP * 9;  // rounds / records per step
@@ -447,11 +456,12 @@ __device__ __forceinline__ void pack_bal_layer(const float* __restrict__ theta, 
     return;
   }
   if (tid < C) {  // the sums start from the diagonal entries' (nearest) rounding errors, taps 0..8
-    float e = 0.f;
+    float e = 0.f;  // (a mirror job: the forward's, W[t][o][o] = -W_bwd[8-t][o][o])
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-      const int32_t v = w_src[(t * C + tid) * C + tid];
-      const float x = v < 0 ? gamma : ((v & 1) ? -th[v >> 1] : th[v >> 1]);
+      const int32_t v = w_src[((mirror ? 8 - t : t) * C + tid) * C + tid];
+      const float x0 = v < 0 ? gamma : ((v & 1) ? -th[v >> 1] : th[v >> 1]);
+      const float x = mirror ? -x0 : x0;
       e = __fadd_rn(e, __fsub_rn((float)(bf16)x, x));
     }
     err[tid] = e;
@@ -538,8 +548,8 @@ __global__ __launch_bounds__(kBalThreads) void k_theta_to_w_pack_bal(PackJobs jo
   const PackJob& J = jobs.j[k];
   const auto args = [&](auto cc) {
     constexpr int C = decltype(cc)::value;
-    pack_bal_layer<C>(J.theta, J.theta_stride, J.w_src, J.gamma, (bf16*)J.w, J.w_stride, J.theta_dst, J.n_theta, b,
-                      lds);
+    pack_bal_layer<C>(J.theta, J.theta_stride, J.w_src, J.gamma, (bf16*)J.w, J.w_stride, J.theta_dst, J.n_theta,
+                      J.mirror != 0, b, lds);
   };
   if (J.C == 16) args(std::integral_constant<int, 16>{});
   else if (J.C == 32) args(std::integral_constant<int, 32>{});
@@ -656,7 +666,7 @@ using namespace asr;
 extern "C" {
 
 const char* asr_last_error(void) { return g_err; }
-int asr_abi_version(void) { return 12; }
+int asr_abi_version(void) { return 13; }
 
 int asr_device_cu_count(void) { return cu_count(); }
 
@@ -750,19 +760,33 @@ int asr_theta_to_w(const float* theta, long theta_stride, int L, int C, const in
   return ASR_OK;
 }
 
+int asr_theta_to_w_mirror(const float* theta, long theta_stride, int L, int C, const int32_t* w_src_bwd, void* w_out,
+                          long w_stride, int dtype, asr_stream_t stream) {
+  if (dtype != ASR_BF16)  // (no rounding, or a bad dtype: asr_theta_to_w's checks)
+    return asr_theta_to_w(theta, theta_stride, L, C, w_src_bwd, 0.f, w_out, w_stride, dtype, stream);
+  if (!theta || !w_src_bwd || !w_out || L < 1 || C < 1 || L > 65535)
+    return fail(ASR_E_ARG, "asr_theta_to_w_mirror: bad arguments");
+  if (C % 16 != 0) return fail(ASR_E_UNSUPPORTED, "asr_theta_to_w_mirror: bf16 pack needs C %% 16 == 0 (C=%d)", C);
+  if (w_stride < asr_wpack_elems(C)) return fail(ASR_E_ARG, "asr_theta_to_w_mirror: w_stride too small");
+  return theta_to_w_bf16(theta, theta_stride, L, C, w_src_bwd, 0.f, w_out, w_stride, true, (hipStream_t)stream, nullptr,
+                         0, true);
+}
+
 }  // extern "C"
 
 namespace asr {
 
 // asr_theta_to_w's bf16 pack: balanced rounding (k_theta_to_w_pack_bal) when
-// `balance` and C <= 64, round to nearest otherwise (ASR_VARIANT_W_BF16)
+// `balance` and C <= 64, round to nearest otherwise (ASR_VARIANT_W_BF16: there the pack of a
+// transposed map is the forward pack's mirror anyway).  mirror: w_src is asr_param_map_transpose's
+// map and the pack takes the forward pack's decisions (PackJob::mirror)
 int theta_to_w_bf16(const float* theta, long theta_stride, int L, int C, const int32_t* w_src, float gamma, void* w,
-                    long w_stride, bool balance, hipStream_t s, const int32_t* theta_dst, long n_theta) {
+                    long w_stride, bool balance, hipStream_t s, const int32_t* theta_dst, long n_theta, bool mirror) {
   const long n = asr_wpack_elems(C);
   if (!theta || !w_src || !w || L < 1 || L > 65535 || n < 0 || w_stride < n)
     return fail(ASR_E_ARG, "theta_to_w_bf16: bad arguments");
   if (balance && (C == 16 || C == 32 || C == 64)) {
-    const PackJob job{theta, theta_stride, L, C, w_src, gamma, w, w_stride, theta_dst, n_theta};
+    const PackJob job{theta, theta_stride, L, C, w_src, gamma, w, w_stride, theta_dst, n_theta, mirror ? 1 : 0};
     ASR_TRY(theta_to_w_bf16_jobs(&job, 1, s));
   } else {
     const int frags = (C / 16) * ((9 * C + 31) / 32);

@@ -192,7 +192,10 @@ def theta_to_w(theta: torch.Tensor, C: int, pmap: ParamMap, gamma: float, dtype:
 
 def theta_to_w_transposed(theta: torch.Tensor, C: int, pmap: ParamMap, dtype: int) -> torch.Tensor:
     """W_bwd = -flip(W)^T for the backward of a non-antisymmetric operator
-    (pass it to conv_backward with gamma 0)."""
+    (pass it to conv_backward with gamma 0).  For every dtype and rounding it
+    is the mirror of theta_to_w's W of the same theta, entry for entry
+    (3 x 3: asr_theta_to_w_mirror, which takes the forward pack's decisions
+    where the bf16 pack is balanced; k != 3 rounds to nearest)."""
     dev = theta.device
     wb = pmap.w_src_bwd(dev)
     if pmap.k != 3:
@@ -212,7 +215,7 @@ def theta_to_w_transposed(theta: torch.Tensor, C: int, pmap: ParamMap, dtype: in
     else:
         per = 9 * C * C
         out = torch.empty(per, dtype=torch.float32, device=dev)
-    _lib.call("asr_theta_to_w", _p(theta), pmap.n_theta, 1, C, _p(wb), 0.0, _p(out), per, dtype, _stream())
+    _lib.call("asr_theta_to_w_mirror", _p(theta), pmap.n_theta, 1, C, _p(wb), _p(out), per, dtype, _stream())
     return out.view(1, 3, 3, C, C) if dtype == ASR_F32 else out.view(1, per)
 
 

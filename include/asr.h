@@ -109,8 +109,8 @@ int asr_param_map(int C, int kind, int antisymmetric, int32_t* w_src, int32_t* t
  * bad arguments.  For such kinds the backward pass applies A^T with the
  * forward W (asr_conv_backward's identity).  Otherwise the caller
  * materialises the transposed operator W_bwd = -flip(W)^T from the map
- * asr_param_map_transpose returns and passes it (with gamma 0) as the
- * backward's w. */
+ * asr_param_map_transpose returns, with asr_theta_to_w_mirror, and passes it
+ * (with gamma 0) as the backward's w. */
 int asr_param_is_antisymmetric(int kind, int antisymmetric);
 int asr_param_map_transpose(int C, const int32_t* w_src, int32_t* w_src_bwd);
 /* Host: the pull-back of an antisymmetric parametrisation (C = 64) from the
@@ -147,6 +147,24 @@ long asr_wpack_elems(int C);
  * read (theta) nor written (w_out). */
 int asr_theta_to_w(const float* theta, long theta_stride, int L, int C, const int32_t* w_src,
                    float gamma, void* w_out, long w_stride, int dtype, asr_stream_t stream);
+
+/* (ABI 13) The backward's W of an operator that is not antisymmetric:
+ * W_bwd = -flip(W)^T of the W that asr_theta_to_w gives for the same theta
+ * (gamma plays no part: such a map has no constant entries).
+ *   w_src_bwd: device copy of asr_param_map_transpose's map of the forward map;
+ *   every other argument as in asr_theta_to_w.
+ * ASR_F32, and ASR_BF16 where asr_theta_to_w rounds to nearest: the same as
+ * asr_theta_to_w on w_src_bwd with gamma 0 (round to nearest even commutes
+ * with negation and with the permutation).  ASR_BF16 with balanced rounding:
+ * the pairs take the forward pack's decisions (the error sums start from the
+ * forward's diagonal errors, not from their negation), so that every entry is
+ * bit for bit the negated entry of the forward pack at the flipped tap and
+ * swapped channels; asr_theta_to_w on w_src_bwd rounds about a quarter of the
+ * entries to the other neighbour, and a backward with it is the gradient of a
+ * slightly different forward.  The caller states that the map is a transpose
+ * by calling this function; nothing is inferred from the map. */
+int asr_theta_to_w_mirror(const float* theta, long theta_stride, int L, int C, const int32_t* w_src_bwd,
+                          void* w_out, long w_stride, int dtype, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Fused antisymmetric 3x3 conv / Euler block

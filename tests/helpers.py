@@ -60,7 +60,7 @@ def _pairs_antisymmetric(src, sign, C):
     return bool(np.all(a >= 0) and np.all(a == b) and np.all(g[:, i, o] == -g[::-1][:, o, i]))
 
 
-def w_bf16_balanced(W, src=None, sign=None):
+def w_bf16_balanced(W, src=None, sign=None, mirrored=False):
     """The bf16 W of the executor's weight pack (asr_theta.hip,
     k_theta_to_w_pack_bal), bit-exact.  Maps whose off-diagonal entries come
     in antisymmetric pairs (W[t][i][o] = -W[8-t][o][i]) round each pair to one
@@ -74,7 +74,12 @@ def w_bf16_balanced(W, src=None, sign=None):
     channel pairs); within a pair (o, i), D = e_o - e_i, and per tap 0..8 the
     upper neighbour iff D + (d_lo + d_hi) < 0, else the lower (a bf16 value
     stays), D += 2d; then e_o += S, e_i -= S for the pair's S = sum d, all in
-    float32.  A map without the pairing (or src=None) rounds to nearest."""
+    float32.  A map without the pairing (or src=None) rounds to nearest.
+    mirrored (PackJob::mirror, asr_theta_to_w_mirror): W is W_bwd =
+    -flip(V)^T of a forward V and src, sign its transposed map; the sums then
+    start from V's diagonal errors, term t from the negated entry of W at tap
+    8 - t (V[t][o][o] itself), so every pair takes V's decision and the
+    result is -flip(w_bf16_balanced(V))^T bit for bit."""
     W32 = np.asarray(W, np.float32).reshape(3, 3, W.shape[2], W.shape[3])
     C = W32.shape[2]
     Q = bf16_round(W32).reshape(9, C, C).copy()
@@ -84,7 +89,8 @@ def w_bf16_balanced(W, src=None, sign=None):
     err = np.zeros(C, np.float32)
     dg = np.arange(C)
     for t in range(9):  # the error sums start from the diagonal entries' (nearest) rounding
-        err = err + (Q[t, dg, dg] - X[t, dg, dg])
+        x = -X[8 - t, dg, dg] if mirrored else X[t, dg, dg]
+        err = err + (bf16_round(x) - x)
     q = np.arange(1, C // 2)
     for r in range(C - 1):
         a = np.concatenate([[C - 1], (r + q) % (C - 1)])
@@ -110,6 +116,18 @@ def w_bf16_balanced(W, src=None, sign=None):
             Q[8 - t, o, i] = -qv
         err[o], err[i] = eo + S, ei - S
     return Q.reshape(W32.shape)
+
+
+def w_mirror(W):
+    """-flip(W)^T of an HWIO [3, 3, C, C] array: the transposed operator's W (asr_param_map_transpose)."""
+    return -np.asarray(W)[::-1, ::-1].transpose(0, 1, 3, 2)
+
+
+def transpose_map(src, sign, C):
+    """(src, sign) of W_bwd = -flip(W)^T (asr_param_map_transpose, for a map without constant entries)."""
+    s = np.asarray(src).reshape(3, 3, C, C)[::-1, ::-1].transpose(0, 1, 3, 2)
+    g = -np.asarray(sign).reshape(3, 3, C, C)[::-1, ::-1].transpose(0, 1, 3, 2)
+    return np.ascontiguousarray(s).reshape(np.shape(src)), np.ascontiguousarray(g).reshape(np.shape(sign))
 
 
 def decode_mask(mask_bytes, N, H, W, C):

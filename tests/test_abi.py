@@ -152,6 +152,20 @@ def test_transposed_operator_map(lib, kind, anti):
         assert np.array_equal(Wb, want)
 
 
+def test_theta_to_w_mirror_checks_its_arguments(lib):
+    """asr_theta_to_w_mirror (ABI 13: W_bwd as the forward pack's mirror) refuses bad arguments before
+    any launch, under its own name."""
+    from differential_equations_resnet_amd import _lib
+    fake = ct.c_void_p(16)  # never dereferenced: the checks come first
+    n = lib.asr_wpack_elems(16)
+    assert lib.asr_theta_to_w_mirror(None, 10, 1, 16, fake, fake, n, _lib.ASR_BF16, None) == _lib.ASR_E_ARG
+    assert b"asr_theta_to_w_mirror" in lib.asr_last_error()
+    assert lib.asr_theta_to_w_mirror(fake, 10, 1, 16, fake, fake, n - 1, _lib.ASR_BF16, None) == _lib.ASR_E_ARG
+    assert b"w_stride" in lib.asr_last_error()
+    assert lib.asr_theta_to_w_mirror(fake, 10, 1, 20, fake, fake, n, _lib.ASR_BF16, None) == _lib.ASR_E_UNSUPPORTED
+    assert lib.asr_theta_to_w_mirror(fake, 10, 1, 16, fake, fake, n, 7, None) == _lib.ASR_E_ARG  # dtype
+
+
 def test_status_and_measurement_entry_points_without_gpu(lib):
     """Without a device the degraded-hand-off count cannot be read (an error
     code, not a count); kernel times need a recorded ASR_VARIANT_TIMED call on

@@ -81,6 +81,8 @@ def test_theta_to_w_bf16_pack_exact(rt, C, kind, anti, gamma, L):
     flat = (np.random.default_rng(C + kind).standard_normal(L * stride) * 0.2).astype(np.float32)
     w = rt.theta_to_w(torch.from_numpy(flat).cuda(), C, pm, gamma, rt.ASR_BF16, layers=L, theta_stride=stride)
     packs = w.view(torch.int16).cpu().numpy().reshape(L, -1)
+    again = rt.theta_to_w(torch.from_numpy(flat).cuda(), C, pm, gamma, rt.ASR_BF16, layers=L, theta_stride=stride)
+    assert np.array_equal(again.view(torch.int16).cpu().numpy().reshape(L, -1), packs)  # deterministic
     ws = pm.w_src.astype(np.int64)
     src, sign = np.where(ws >= 0, ws >> 1, -1), np.where(ws & 1, -1, 1)
     for l in range(L):
@@ -90,6 +92,113 @@ def test_theta_to_w_bf16_pack_exact(rt, C, kind, anti, gamma, L):
         np.testing.assert_array_equal(_unpack_bf16(got, C).view(np.uint32), want.view(np.uint32))
         if kind != 2 and C <= 64:  # balanced: differs from nearest somewhere, exactly antisymmetric off the diagonal
             assert not np.array_equal(want, bf16_round(W))
+
+
+def _pack_slots(C):
+    """Boolean mask over the pack's elements: True where an entry of W lives (the rest is padding, kappa >= 9C)."""
+    used = np.zeros((C // 16) * ((9 * C + 31) // 32) * 512, bool)
+    idx = _unpack_bf16(np.arange(used.size), C)
+    assert np.unique(idx).size == 9 * C * C
+    used[idx.ravel()] = True
+    return used
+
+
+@pytest.mark.parametrize("C,kind,balanced", [(16, 1, True), (32, 1, True), (64, 1, True), (16, 2, False),
+                                             (128, 1, False)])
+def test_theta_to_w_transposed_bf16_is_the_forward_packs_mirror(rt, C, kind, balanced):
+    """The backward's pack of an operator that is not antisymmetric (theta_to_w_transposed,
+    asr_theta_to_w_mirror) against the forward's (theta_to_w, gamma 0) of the same theta: every entry
+    is the negated entry of the forward pack at the flipped tap and swapped channels, as float values
+    (+0 and -0 compare equal: a theta of exactly 0 may give either, and the conv kernels cannot tell
+    them apart); apart from a zero's sign every bit is therefore identical; the pack's padding is
+    zero.  General kind with antisymmetric=False at C <= 64: the balanced rounding, where the forward
+    pack differs from round to nearest and the mirror needs the forward's decisions.  The regular kind
+    and C = 128 round to nearest (controls).  One layer per call (theta_to_w_transposed's interface),
+    2 layers."""
+    L = 2
+    pm = rt.param_map(C, kind, False)
+    n = pm.n_theta
+    flat = (np.random.default_rng(C + kind).standard_normal(L * n) * 0.2).astype(np.float32)
+    ws = pm.w_src.astype(np.int64)
+    src, sign = np.where(ws >= 0, ws >> 1, -1), np.where(ws & 1, -1, 1)
+    used = _pack_slots(C)
+    for l in range(L):
+        th = torch.from_numpy(flat[l * n:(l + 1) * n]).cuda()
+        fwd = rt.theta_to_w(th, C, pm, 0.0, rt.ASR_BF16).view(torch.int16).cpu().numpy().ravel().view(np.uint16)
+        bwd = rt.theta_to_w_transposed(th, C, pm, rt.ASR_BF16).view(torch.int16).cpu().numpy().ravel().view(np.uint16)
+        assert fwd.size == bwd.size == used.size
+        assert not fwd[~used].any() and not bwd[~used].any()  # padding: zero bits
+        Wf = _unpack_bf16((fwd.astype(np.uint32) << 16).view(np.float32), C)
+        Wb = _unpack_bf16((bwd.astype(np.uint32) << 16).view(np.float32), C)
+        want = -Wf[::-1, ::-1].transpose(0, 1, 3, 2)
+        bad = Wb != want  # float comparison: +0 == -0
+        assert not bad.any(), f"layer {l}: {int(bad.sum())} of {bad.size} entries differ from -flip(W)^T"
+        nz = want != 0
+        assert np.array_equal(Wb[nz].view(np.uint32), want[nz].view(np.uint32))  # every other bit identical
+        W = O.assemble_from_map(flat[l * n:(l + 1) * n].astype(np.float64), C, src, sign, 0.0)
+        assert np.array_equal(Wf, bf16_round(W)) != balanced  # balanced cases differ from nearest somewhere
+
+
+def _mirror_pack(pack_u16, C):
+    """The pack (uint16 bf16 bits) of -flip(W)^T from the pack of W: the sign bit flipped, the entries
+    permuted, the padding zero."""
+    idx = _unpack_bf16(np.arange(pack_u16.size), C)  # HWIO position -> pack slot
+    bits = pack_u16[idx] ^ np.uint16(0x8000)
+    out = np.zeros_like(pack_u16)
+    out[idx.ravel()] = bits[::-1, ::-1].transpose(0, 1, 3, 2).ravel()
+    return out
+
+
+def _executor_packs(rt, params, blocks, kind, anti, gamma):
+    """[(name, forward pack bytes, mirror pack bytes)] of the blocks [(name, C, theta offset)]"""
+    out = []
+    for name, C, off in blocks:
+        pm = rt.param_map(C, kind, anti)
+        w = rt.theta_to_w(params[off:off + pm.n_theta].contiguous(), C, pm, gamma, rt.ASR_BF16)
+        fwd = w.view(torch.int16).cpu().numpy().ravel().view(np.uint16)
+        out.append((name, fwd.tobytes(), _mirror_pack(fwd, C).tobytes()))
+    return out
+
+
+def _net_case(rt, kind, anti):
+    C, L, N = 16, 2, 2
+    ex = rt.NetExecutor(N, 32, 32, 3, C, L, 10, 0.5, 0.0, 127.5, 127.5, dtype="bfloat16", param_kind=kind,
+                        antisymmetric=anti)
+    nt = rt.param_map(C, kind, anti).n_theta
+    return ex, [(f"block{l}", C, 27 * C + C + l * (nt + C)) for l in range(L)]
+
+
+def _stages_case(rt, kind, anti):
+    ex = rt.StagesExecutor(2, 32, 32, 3, [(16, 1, 0), (32, 1, 2)], 10, 0.5, 0.0, 127.5, 127.5, dtype="bfloat16",
+                           param_kind=kind, antisymmetric=anti)
+    nt16 = rt.param_map(16, kind, anti).n_theta
+    off1 = 27 * 16 + 16 + nt16 + 16 + (9 * 16 * 32 + 32 + 16 * 32 + 32)  # conv1, stage 0's block, the transition
+    return ex, [("stage0/block0", 16, 27 * 16 + 16), ("stage1/block0", 32, off1)]
+
+
+@pytest.mark.parametrize("case", [_net_case, _stages_case], ids=["net", "stages"])
+def test_executors_hold_the_forward_pack_and_its_mirror(rt, case):
+    """After one training step of a bf16 network whose operator is not antisymmetric (general kind,
+    antisymmetric=False), the executor's workspace holds, for every block, the bytes of the block's
+    forward pack (asr_theta_to_w on its theta) and the bytes of that pack's mirror -flip(W)^T: the
+    backward's W is the forward's, under the same rule as runtime.theta_to_w_transposed, at L = 2 through
+    the layer stride (net) and through the stages' one launch of several jobs.  The workspace's layout
+    is not assumed: the packs are searched for.  Control: the search finds the forward pack of a 3by3
+    network too (whose backward reuses it)."""
+    for kind, anti, mirror in ((rt.ASR_PARAM_GENERAL, False, True), (rt.ASR_PARAM_3BY3, True, False)):
+        ex, blocks = case(rt, kind, anti)
+        rng = np.random.default_rng(7)
+        params = torch.from_numpy((rng.standard_normal(ex.n_params) * 0.2).astype(np.float32)).cuda()
+        imgs = torch.from_numpy(rng.integers(0, 256, (2, 32, 32, 3)).astype(np.uint8)).cuda()
+        onehot = torch.from_numpy(np.eye(10, dtype=np.float32)[rng.integers(0, 10, 2)]).cuda()
+        ex.forward_backward(params, imgs, onehot)
+        torch.cuda.synchronize()
+        ws = ex.ws.cpu().numpy().tobytes()
+        for name, fwd, mir in _executor_packs(rt, params, blocks, kind, anti, 0.0):
+            assert ws.find(fwd) >= 0, f"{name}: the forward pack is not in the workspace (kind {kind})"
+            if mirror:
+                assert fwd != mir
+                assert ws.find(mir) >= 0, f"{name}: the mirror of the forward pack is not in the workspace"
 
 
 def _run_forward(rt, mode, x_np, th, b, C, gamma, h, dtype):

@@ -20,8 +20,8 @@ def lib():
     return _lib.load(build_if_missing=True)
 
 
-def test_abi_version_unchanged(lib):
-    assert lib.asr_abi_version() == 12
+def test_abi_version(lib):
+    assert lib.asr_abi_version() == 13
 
 
 @pytest.mark.parametrize("kind,flags,want", [

@@ -28,10 +28,10 @@ def _check(lib, rows, n_params):
 # --------------------------------------------------------------------------
 # binding and check
 # --------------------------------------------------------------------------
-def test_binding_exists_and_abi_is_still_12(lib):
+def test_binding_exists_and_abi_version(lib):
     bound = {n for n, _, _ in _lib.SIGNATURES}
     assert {"asr_regularize_check", "asr_regularize_workspace_bytes", "asr_regularize"} <= bound
-    assert _lib.ABI_VERSION == 12 and lib.asr_abi_version() == 12
+    assert _lib.ABI_VERSION == 13 and lib.asr_abi_version() == 13
     assert _lib.ASR_REG_MAX_SEGMENTS == 256 and ct.sizeof(_lib.RegSegment) == 40
 
 

@@ -22,8 +22,8 @@ def _net(C, W, N=4, H=8, L=2, integrator=0, kernel_size=0, param_kind=0, variant
                           variant, kernel_size, 0)
 
 
-def test_abi_version_is_12(lib):
-    assert lib.asr_abi_version() == 12 == _lib.ABI_VERSION
+def test_abi_version(lib):
+    assert lib.asr_abi_version() == 13 == _lib.ABI_VERSION
 
 
 @pytest.mark.parametrize("C", [128, 256])

@@ -6,7 +6,7 @@ tests/test_gpu_kernels.py (test_theta_to_w_bf16_pack_exact)."""
 import numpy as np
 import pytest
 
-from helpers import bf16_round, w_bf16_balanced
+from helpers import bf16_round, transpose_map, w_bf16_balanced, w_mirror
 from oracle import asr_oracle as O
 
 
@@ -56,6 +56,57 @@ def test_unpaired_map_rounds_to_nearest():
     src2 = src.copy()
     src2[np.flatnonzero(src2 >= 0)[5]] = int(src.max()) + 1  # break one pair
     assert np.array_equal(w_bf16_balanced(W3, src2, sign), bf16_round(W3))
+
+
+def _general_false(C):
+    """(W, W_bwd = -flip(W)^T, its map) of the general kind, antisymmetric=False, theta ~ 0.2 N(0, 1), seed C."""
+    W, src, sign = _w(C, "general", False, 0.0, C)
+    srcb, signb = transpose_map(src, sign, C)
+    n = int(src.max()) + 1
+    th = (np.random.default_rng(C).standard_normal(n) * 0.2).astype(np.float32)
+    Wb = O.assemble_from_map(th.astype(np.float64), C, srcb, signb, 0.0).astype(np.float32)
+    assert np.array_equal(Wb, w_mirror(W))  # (the transposed map is the mirror's map)
+    return W, src, sign, Wb, srcb, signb
+
+
+@pytest.mark.parametrize("C", [16, 32, 64])
+def test_mirrored_pack_is_the_mirror_of_the_forward_pack(C):
+    """The backward's W of an operator that is not antisymmetric, W_bwd = -flip(W)^T, packed in the
+    mirrored mode is the mirror of the forward pack bit for bit (signed zeros included: negation is
+    exact): the backward reads the W that the forward read.  It is still a balanced pack."""
+    W, src, sign, Wb, srcb, signb = _general_false(C)
+    Q = w_bf16_balanced(W, src, sign)
+    assert not np.array_equal(Q, bf16_round(W))  # the case balances
+    Qb = w_bf16_balanced(Wb, srcb, signb, mirrored=True)
+    assert np.array_equal(Qb.view(np.uint32), w_mirror(Q).view(np.uint32))
+
+
+# entries of pack(W_bwd) that differ from mirror(pack(W)) under the unmirrored rule, each by one bf16 ulp
+# (general kind, antisymmetric=False, theta ~ 0.2 N(0, 1), seed C)
+UNMIRRORED_MISMATCHES = {16: 602, 32: 2504, 64: 9492}
+
+
+@pytest.mark.parametrize("C", [16, 32, 64])
+def test_unmirrored_pack_of_the_transposed_map_is_another_w(C):
+    """Why the mirrored mode exists: the transposed map keeps every off-diagonal entry and negates the
+    diagonal, so a plain balanced pack of it starts every channel's error sum from the opposite sign
+    and rounds about a quarter of the entries to the other neighbour than the forward pack did."""
+    W, src, sign, Wb, srcb, signb = _general_false(C)
+    want = w_mirror(w_bf16_balanced(W, src, sign))
+    got = w_bf16_balanced(Wb, srcb, signb)
+    bad = got != want
+    assert int(bad.sum()) == UNMIRRORED_MISMATCHES[C]
+    lo = np.vectorize(lambda v: _neighbours(v)[0])(Wb)
+    hi = np.vectorize(lambda v: _neighbours(v)[1])(Wb)
+    assert np.all(((got == lo) & (want == hi) | (got == hi) & (want == lo))[bad])  # one ulp: the other neighbour
+    i = np.arange(C)
+    assert not bad.reshape(9, C, C)[:, i, i].any()  # the diagonal rounds to nearest either way
+
+
+def test_mirrored_mode_leaves_unpaired_maps_to_nearest():
+    W = np.random.default_rng(0).standard_normal((3, 3, 16, 16)).astype(np.float32)
+    src = np.arange(9 * 16 * 16)
+    assert np.array_equal(w_bf16_balanced(W, src, np.ones_like(src), mirrored=True), bf16_round(W))
 
 
 def test_vectorised_restatement_equals_scalar_greedy():
